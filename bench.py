@@ -14,11 +14,18 @@ waves, where pushes per origin-round settle near 3N).
 value = pushes to non-failed peers over all slots and ranks / wall time of the K
 timed steps (max over ranks).
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints
+the result line; its roofline figures come from the timed steps themselves. --dump-outputs DIR
+also writes what the last timed step returned (dump_outputs below). Everything that takes a
+run of its own -- `steady_state`, `cpu_baseline`, `cpu_baseline_1core`, the c4 / c3 / c5 legs
+and, at N > 1, `weak_trial` -- runs only with --full (and --no-steady, --no-cpu-baseline,
+--no-large then leave single ones out). --only-large and --workload are runs of their own.
+
 Multi-GPU (one process per GPU, no data-path collective). Default --scaling strong: the
 ranks split the 3,000 origins of ONE C2 trial (same seed; rank r takes origins
 [r*S/K, (r+1)*S/K)) -- the north star's origin-sharded sweep; with --check-shard rank 0
 checks the gathered per-round summaries of every origin against all origins run on one
-engine. At N > 1 the line also carries `weak_trial`: the ranks then run independent C2
+engine. At N > 1 with --full the line also carries `weak_trial`: the ranks then run independent C2
 trials (rank r: all 3,000 origins, Philox seed + r), the per-GPU work of one C2 at every N.
 --scaling weak makes that the headline instead. --workload c4 / c5 run BASELINE C4's 13
 sweep sims (1M nodes) / C5's 16 origins (10M nodes) instead, dealt over the ranks (strong)
@@ -34,7 +41,7 @@ cpu_baseline: the oracle (reference-structure C++ restatement: maps keyed by
 32-byte pubkeys, one origin per sim) on all host cores (independent origin-sims
 dealt over std::threads) on a bounded sample of the same workload;
 cpu_baseline_1core: the same code on one core.
-Secondary legs at N = 1 (reported beside `value`, never part of it):
+Secondary legs at N = 1 with --full (reported beside `value`, never part of it):
   c4: BASELINE C4 as configured -- 1M-node network, origin rank 1, the fail-nodes
       sweep (0.1..0.5, when-to-fail 0) and the prune-stake-threshold sweep
       (0.05..0.40) as 13 slots of one engine; the propagation path's B_prop
@@ -528,6 +535,45 @@ def c3_sweep_workload(gs, synth, args, rank, world, dev, barrier, reduce):
             "origin_rounds_per_s": sims_total * args.steps / dt, "cpu_baseline": None}
 
 
+# ---------------------------------------------------------------- --dump-outputs ----
+DUMP_HOPS_BYTES = 40 << 20      # float32 hop rows
+DUMP_COUNTER_BYTES = 8 << 20    # float32 egress / ingress / prune counter rows (three arrays)
+
+
+def dump_outputs(eng, summ, out_dir, prefix=""):
+    """--dump-outputs: what the last timed step handed its caller, as float .npy files (under
+    64 MB in all), so that two builds run with the same arguments compare output for output.
+      round_summaries.npy  float64 [slots, fields]: the step's RoundSummary of every slot
+                           (the fields of gossip_hip.h in order, without the padding word)
+      hops.npy             float32 [k, nodes]: Engine.hops of the slots in hop_slots.npy
+      egress.npy / ingress.npy / prune_counts.npy
+                           float32 [m, nodes]: Engine.counters of the slots in counter_slots.npy
+    The slot lists are every slot while the rows fit the budgets above, else a fixed seeded
+    sample (sorted)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+    def pick(budget, row_bytes):
+        k = max(1, min(eng.n_slots, budget // row_bytes))
+        if k == eng.n_slots:
+            return np.arange(k)
+        return np.sort(np.random.default_rng(0x5EED).choice(eng.n_slots, size=k, replace=False))
+
+    last = summ[-1]
+    save("round_summaries", np.stack([last[f].astype(np.float64) for f in summ.dtype.names if f != "pad0"], axis=1))
+    slots = pick(DUMP_HOPS_BYTES, 4 * eng.n)
+    save("hop_slots", slots.astype(np.float64))
+    save("hops", np.stack([eng.hops(int(k)) for k in slots]).astype(np.float32))
+    slots = pick(DUMP_COUNTER_BYTES, 12 * eng.n)
+    save("counter_slots", slots.astype(np.float64))
+    rows = [eng.counters(int(k)) for k in slots]
+    for j, name in enumerate(("egress", "ingress", "prune_counts")):
+        save(name, np.stack([r[j] for r in rows]).astype(np.float32))
+
+
 # ------------------------------------------------------------------------ main ----
 def main():
     ap = argparse.ArgumentParser()
@@ -545,11 +591,16 @@ def main():
     ap.add_argument("--bfs-mode", type=int, default=0)
     ap.add_argument("--large-mode", type=int, default=0, help="BFS mode of the c4/c3 legs (0 = AUTO)")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary measurements: the steady-state window, the "
+                         "CPU baselines, the c4 / c3 / c5 legs and (N > 1) the weak-scaling trial")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (round summaries, hops, counters) as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-steady", action="store_true")
+    ap.add_argument("--no-steady", action="store_true", help="with --full: skip the steady-state window")
     ap.add_argument("--split-round", action="store_true", help="step kernels instead of the one-kernel round")
-    ap.add_argument("--no-large", action="store_true", help="skip the c4 / c3 legs")
+    ap.add_argument("--no-large", action="store_true", help="with --full: skip the c4 / c3 / c5 legs")
     ap.add_argument("--only-large", action="store_true", help="run only the c4 / c3 legs (A/B of BFS modes)")
     ap.add_argument("--legs", default="c4,c3", help="with --only-large: which legs (e.g. c4 for a PMC pass)")
     ap.add_argument("--c4-sims", default="", help="c4 leg: only these of the 13 sweep sims (e.g. 0,8: a rank's share)")
@@ -574,8 +625,10 @@ def main():
     # seed + r). At N = 1 both are the same run.
     args.shard_origins = args.scaling == "strong"
     args.per_rank_networks = args.scaling == "weak"
+    if args.dump_outputs and (args.only_large or args.workload != "c2"):
+        ap.error("--dump-outputs writes the headline (c2) workload's outputs")
 
-    gs = load_pkg()          # loads libgossip_hip.so (and its HIP runtime) before torch, if torch is used at all
+    gs = load_pkg()         # loads libgossip_hip.so (and its HIP runtime) before torch, if torch is used at all
     gs.lib()
     import gossip_sim_amd.synth as synth
 
@@ -650,6 +703,8 @@ def main():
     dt_local = time.perf_counter() - t0
     summ = eng.summaries()  # [steps, S]
     assert summ.shape[0] == args.steps
+    if args.dump_outputs:
+        dump_outputs(eng, summ, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "")
     E = float(summ["pushes"].astype("float64").sum())
     V = float(summ["visited"].astype("float64").sum())
     einfo = eng.info()
@@ -696,7 +751,7 @@ def main():
             if not shard_check:
                 raise SystemExit("origin-sharded summaries differ from the one-engine run")
     weak_trial = None
-    if world > 1 and args.shard_origins:  # the same ranks as independent trials: rank r = all origins, seed + r
+    if args.full and world > 1 and args.shard_origins:  # the same ranks as independent trials: rank r = all origins, seed + r
         eng.close()
         wt = gs.Engine(stakes, S_all, fanout=args.fanout, active_set_size=args.active_set_size,
                        rotation_probability=args.rotation_probability, seed=args.seed + rank, device=dev,
@@ -720,7 +775,7 @@ def main():
                       "scaling": "weak", "parallelism": f"trial-sharded x{world} (rank r: all {S_all} origins, "
                                                         f"Philox seed + r)"}
     steady = None
-    if not args.no_steady and world == 1 and args.warmup + args.steps <= 60:
+    if args.full and not args.no_steady and world == 1 and args.warmup + args.steps <= 60:
         for r in range(args.warmup + args.steps, 60):
             eng.round(r, record=False)
         eng.sync()
@@ -782,10 +837,10 @@ def main():
     }
     if eng is not None:
         eng.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_all(pks, stakes, args)
         out["cpu_baseline_1core"] = cpu_baseline_1core(pks, stakes, args, args.cpu_budget)
-    if rank == 0 and world == 1 and not args.no_large:
+    if args.full and rank == 0 and world == 1 and not args.no_large:
         out["c4"] = c4_leg(gs, synth, args)
         out["c3"] = c3_leg(gs, synth, args)
         out["c5"] = c5_leg(gs, synth, args)

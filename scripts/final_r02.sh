@@ -11,7 +11,7 @@ if [ "${SKIP_C5:-0}" != 1 ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
   timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-    python3 bench.py > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+    python3 bench.py --full > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
   grep -h '"metric"' $OUT/bench.log | tail -1 > $OUT/bench.json
   cut -c1-1500 $OUT/bench.json
 fi

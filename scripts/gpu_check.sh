@@ -31,7 +31,7 @@ if [ "$MODE" = all ] || [ "$MODE" = pmc ]; then
     cp gpurun_out/pmc_k_round_wg_3000x3000.json $ROUND_DIR/
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   tail -1 gpurun_out/bench.log > gpurun_out/bench.json
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then

@@ -27,17 +27,17 @@ if [ "${PMC:-1}" = 1 ]; then
 fi
 
 if [ "${DEF:-1}" = 1 ]; then
-  timeout -k 10 600 python3 bench.py > $OUT/bench_default.log 2>&1 || { tail -20 $OUT/bench_default.log; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.log 2>&1 || { tail -20 $OUT/bench_default.log; exit 1; }
   grep '"metric"' $OUT/bench_default.log | tail -1 > $OUT/bench_default.json
   echo "default: $(cut -c1-300 $OUT/bench_default.json)"
 fi
 if [ "${DRV:-1}" = 1 ]; then
-  timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1 || { tail -20 $OUT/bench_driver.log; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1 || { tail -20 $OUT/bench_driver.log; exit 1; }
   grep '"metric"' $OUT/bench_driver.log | tail -1 > $OUT/bench_driver_window.json
   echo "driver: $(cut -c1-300 $OUT/bench_driver_window.json)"
 fi
 if [ "${PROF:-1}" = 1 ]; then
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; }
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; }
   grep '"metric"' $OUT/prof.log | tail -1 > $OUT/bench_traced.json
 fi

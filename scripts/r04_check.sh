@@ -11,7 +11,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   if [ $rc -ne 0 ]; then grep -E "FAILED|Error|error" $OUT/gpu_tests.log | head -20; exit $rc; fi
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  timeout -k 10 ${BENCH_TO:-600} python3 bench.py ${BENCH_ARGS:---steps 20 --warmup 5} > $OUT/bench.log 2>&1 || { tail -30 $OUT/bench.log; exit 1; }
+  timeout -k 10 ${BENCH_TO:-600} python3 bench.py ${BENCH_ARGS:---full --steps 20 --warmup 5} > $OUT/bench.log 2>&1 || { tail -30 $OUT/bench.log; exit 1; }
   grep -h '"metric"' $OUT/bench.log | tail -1 > $OUT/bench.json
   cut -c1-2500 $OUT/bench.json
 fi

@@ -82,7 +82,7 @@ fi
 if has trace; then
   echo "== trace"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; }
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; }
   python3 scripts/trace_window.py --csv $OUT/prof/run_kernel_trace.csv --kernel k_round_wg --first 5 --count 20 \
     --bench-args "--warmup 5 --steps 20" --out $P/trace_k_round_wg_c2_r5-24.json || exit 1
   cp $OUT/prof/run_kernel_stats.csv $P/rocprof_kernel_stats_driver_window.csv
@@ -108,7 +108,7 @@ fi
 
 if has bench; then
   echo "== bench driver window"
-  timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1 || { tail -20 $OUT/bench_driver.log; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1 || { tail -20 $OUT/bench_driver.log; exit 1; }
   grep '"metric"' $OUT/bench_driver.log | tail -1 > $P/bench_driver_window.json
   cut -c1-400 $P/bench_driver_window.json
 fi

@@ -12,6 +12,6 @@ for s in 3000 1500 750 375; do
 done
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -5 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
 grep '"metric"' $OUT/bench_default.log | tail -1 | cut -c1-200
 TAG=${TAG:-close} bash scripts/r05_mg.sh
