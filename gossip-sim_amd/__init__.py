@@ -105,6 +105,8 @@ EXPORTS = {
     "gs_create": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "gs_destroy": (None, [C.c_void_p]),
     "gs_set_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "gs_set_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gs_get_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gs_sync": (C.c_int, [C.c_void_p]),
     "gs_init_active_sets": (C.c_int, [C.c_void_p]),
     "gs_set_active_set_entry": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
@@ -144,6 +146,8 @@ EXPORTS = {
     "gs_stat_collection_calculate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "gs_run_simulations": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gs_run_simulations_fanouts": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gs_result_free": (None, [C.c_void_p]),
     "gs_result_f64": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_size_t]),
     "gs_result_u64": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_size_t]),
@@ -284,6 +288,22 @@ class Engine:
         th = np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (S,))
         arr = (Slot * S)(*[Slot(int(o), int(m), float(t)) for o, m, t in zip(origins, mi, th)])
         _check(lib().gs_set_slots(self.h, C.cast(arr, C.c_void_p), S))
+
+    def set_slot_fanouts(self, fanouts):
+        """Per-slot push fanouts, each in [1, the engine's `fanout`] (its capacity); None restores
+        the uniform value. Takes effect at the next run_gossip / round."""
+        if fanouts is None:
+            _check(lib().gs_set_slot_fanouts(self.h, None))
+            return
+        f = np.ascontiguousarray(fanouts, dtype=np.uint32)
+        if f.shape != (self.n_slots,):
+            raise ValueError(f"set_slot_fanouts: need exactly {self.n_slots} values")
+        _check(lib().gs_set_slot_fanouts(self.h, _ptr(f)))
+
+    def slot_fanouts(self):
+        out = np.zeros(self.n_slots, dtype=np.uint32)
+        _check(lib().gs_get_slot_fanouts(self.h, _ptr(out)))
+        return out
 
     def init_active_sets(self):
         _check(lib().gs_init_active_sets(self.h))
@@ -498,8 +518,9 @@ class SimResult:
 def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, thresholds=None, fractions=None,
                     fanout=6, asz=12, iterations=1, warm_up=200, p=0.013333, thr=0.15, min_ingress_nodes=2,
                     fraction_to_fail=0.1, when_to_fail=0, nb_stranded=10, nb_message=5, nb_hops=15, test_type=0,
-                    seed=0, device=0, bfs_mode=GS_BFS_AUTO):
-    """gossip_main.rs run_simulation for n_sims sims sharing one trajectory (one engine)."""
+                    seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None):
+    """gossip_main.rs run_simulation for n_sims sims sharing one trajectory (one engine).
+    fanouts: a push fanout per sim (the engine's capacity is their maximum; `fanout` is unused then)."""
     st = np.ascontiguousarray(stakes, dtype=np.uint64)
     cfg = SimConfig(fanout, asz, iterations, warm_up, min_ingress_nodes, when_to_fail, p, thr, fraction_to_fail,
                     nb_stranded, nb_message, nb_hops, test_type, seed, device, bfs_mode)
@@ -509,8 +530,12 @@ def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, th
 
     r, mi, th, fr = arr(origin_ranks, np.uint32), arr(min_ingress, np.uint32), arr(thresholds, np.float64), \
         arr(fractions, np.float64)
+    fo = arr(fanouts, np.uint32)
+    if fo is not None and fo.shape != (n_sims,):
+        raise ValueError(f"run_simulations: fanouts needs exactly n_sims = {n_sims} values")
     h = C.c_void_p()
-    _check(lib().gs_run_simulations(C.byref(cfg), _ptr(st), len(st), n_sims,
-                                    None if r is None else _ptr(r), None if mi is None else _ptr(mi),
-                                    None if th is None else _ptr(th), None if fr is None else _ptr(fr), C.byref(h)))
+    _check(lib().gs_run_simulations_fanouts(C.byref(cfg), _ptr(st), len(st), n_sims,
+                                            None if r is None else _ptr(r), None if mi is None else _ptr(mi),
+                                            None if th is None else _ptr(th), None if fr is None else _ptr(fr),
+                                            None if fo is None else _ptr(fo), C.byref(h)))
     return SimResult(h, n_sims)

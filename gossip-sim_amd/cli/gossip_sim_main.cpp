@@ -3,9 +3,12 @@
 //
 // Same flags, defaults, validation and test-type sweeps as the reference. A sweep's
 // simulations that share one active-set trajectory (no-test, origin-rank,
-// min-ingress-nodes, prune-stake-threshold, fail-nodes) run as slots of ONE engine;
-// engine-changing test types (active-set-size, push-fanout, rotate-probability) give
-// each value its own engine. With --gpus K the simulations are dealt over K devices,
+// min-ingress-nodes, prune-stake-threshold, fail-nodes) run as slots of ONE engine. So do
+// the sims of a push-fanout sweep that share an active-set size (the fanout is a per-slot
+// value of the engine; the reference raises a sim's set size to its fanout, which splits the
+// sweep into one engine per size). The test types that change the trajectory itself
+// (active-set-size, rotate-probability) give each value its own engine. --engine-plan FILE
+// writes the engines of a run. With --gpus K the simulations are dealt over K devices,
 // one host thread and engine per device (results do not depend on the split: the
 // Philox contract makes every slot a pure function of its own parameters).
 //
@@ -69,7 +72,7 @@ struct Cli {
   uint64_t when_to_fail = 0, warm_up = 200;
   // engine / offline extensions
   uint64_t synthetic = 0, seed = 0x5EED0003ull, gpus = 1, bfs_mode = GS_BFS_AUTO;
-  std::string save_results, replay_results;
+  std::string save_results, replay_results, engine_plan;
   std::string influx_file;  // offline Influx line protocol (gs_influx.cpp)
   uint64_t influx_time_base = 0;
 };
@@ -92,6 +95,7 @@ void usage() {
       "  --synthetic N        the deterministic synthetic power-law network of N nodes instead of RPC\n"
       "  --seed S [0x5EED0003] --gpus K [1] --bfs-mode 0..5 [0 = auto; 1 workgroup, 2 level, 3 binned, 4 multi, 5 hybrid]\n"
       "  --save-results PATH  --replay-results PATH (print the report of a saved run, no GPU)\n"
+      "  --engine-plan PATH   write one line per engine: device, simulations, active-set size, fanouts\n"
       "  --influx-file PATH   write the Influx series (influx_db.rs) as line protocol to PATH\n"
       "  --influx-time-base NS  reproducible Influx timestamps NS + 1000 k (default: wall clock)\n"
       "gossip-sim write-accounts --account-file PATH --synthetic N [--num-nodes K] [--zero-stakes] [-f]");
@@ -162,6 +166,7 @@ Cli parse(int argc, char** argv) {
     else if (a == "--bfs-mode") u64(i, c.bfs_mode);
     else if (a == "--save-results") c.save_results = need(i);
     else if (a == "--replay-results") c.replay_results = need(i);
+    else if (a == "--engine-plan") c.engine_plan = need(i);
     else if (a == "--influx-file") c.influx_file = need(i);
     else if (a == "--influx-time-base") u64(i, c.influx_time_base);
     else die(2, "unexpected argument '" + a + "' (see --help)");
@@ -207,6 +212,8 @@ struct Job {
   std::vector<size_t> sims;  // global simulation indices
   std::vector<uint32_t> ranks, mi;
   std::vector<double> thr, frac;
+  std::vector<uint32_t> fanouts;  // per simulation
+  bool slot_fanouts = false;      // a push-fanout sweep: the engine takes `fanouts` per slot
 };
 
 void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsrep::SimArrays>& out,
@@ -214,8 +221,9 @@ void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsre
   gs_sim_config cfg = j.cfg;
   cfg.device = j.device;
   gs_sim_result* r = nullptr;
-  const int rc = gs_run_simulations(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
-                                    j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(), &r);
+  const int rc = gs_run_simulations_fanouts(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+                                            j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(),
+                                            j.slot_fanouts ? j.fanouts.data() : nullptr, &r);
   if (rc) {
     err = std::string("gs_run_simulations: ") + gs_last_error();
     return;
@@ -359,14 +367,9 @@ int main(int argc, char** argv) {
                    ", origin_rank: " + std::to_string(q.origin_rank));
   }
 
-  std::vector<gsrep::SimArrays> sims(num_sims);
-  if (!c.replay_results.empty()) {
-    std::string err;
-    if (!gsrep::load_results(c.replay_results, sims, err)) die(1, err);
-    if (sims.size() != num_sims) die(1, "results file holds " + std::to_string(sims.size()) + " simulations, not " +
-                                            std::to_string(num_sims));
-  } else if (num_sims) {
-    // engines: sims sharing (fanout, active-set size, rotation probability) batch into one
+  // engines: sims sharing (active-set size, rotation probability) batch into one
+  std::vector<Job> jobs;
+  if (num_sims) {
     auto base_cfg = [&](const gsrep::SimParams& q) {
       gs_sim_config cfg{};
       cfg.push_fanout = (uint32_t)q.gossip_push_fanout;
@@ -386,33 +389,68 @@ int main(int argc, char** argv) {
       cfg.bfs_mode = (uint32_t)c.bfs_mode;
       return cfg;
     };
-    const bool per_value_engine = test_type == gsrep::ACTIVE_SET_SIZE || test_type == gsrep::PUSH_FANOUT ||
-                                  test_type == gsrep::ROTATE_PROBABILITY;
-    std::vector<std::vector<size_t>> groups;
+    const bool per_value_engine = test_type == gsrep::ACTIVE_SET_SIZE || test_type == gsrep::ROTATE_PROBABILITY;
+    // batches: sims that share a trajectory, in simulation order
+    std::vector<std::vector<size_t>> batches;
     if (per_value_engine) {
-      for (size_t i = 0; i < num_sims; ++i) groups.push_back({i});
-    } else {  // one batch, split into contiguous chunks over the devices
-      const size_t K = std::min<size_t>(c.gpus, num_sims);
-      for (size_t d = 0; d < K; ++d) {
-        std::vector<size_t> g;
-        for (size_t i = num_sims * d / K; i < num_sims * (d + 1) / K; ++i) g.push_back(i);
-        groups.push_back(g);
+      for (size_t i = 0; i < num_sims; ++i) batches.push_back({i});
+    } else if (test_type == gsrep::PUSH_FANOUT) {  // the sims of one (raised) active-set size
+      for (size_t i = 0; i < num_sims; ++i) {
+        size_t b = 0;
+        while (b < batches.size() &&
+               params[batches[b][0]].gossip_active_set_size != params[i].gossip_active_set_size)
+          ++b;
+        if (b == batches.size()) batches.emplace_back();
+        batches[b].push_back(i);
       }
+    } else {
+      batches.emplace_back();
+      for (size_t i = 0; i < num_sims; ++i) batches[0].push_back(i);
     }
-    std::vector<Job> jobs;
+    // a batch is split into contiguous chunks over the devices
+    std::vector<std::vector<size_t>> groups;
+    for (const auto& b : batches) {
+      const size_t K = std::min<size_t>(c.gpus, b.size());
+      for (size_t d = 0; d < K; ++d)
+        groups.emplace_back(b.begin() + b.size() * d / K, b.begin() + b.size() * (d + 1) / K);
+    }
     for (size_t gi = 0; gi < groups.size(); ++gi) {
       Job j;
       j.cfg = base_cfg(params[groups[gi][0]]);
       j.device = (int)(gi % c.gpus);
       j.sims = groups[gi];
+      j.slot_fanouts = test_type == gsrep::PUSH_FANOUT;
       for (size_t i : groups[gi]) {
         j.ranks.push_back((uint32_t)params[i].origin_rank);
         j.mi.push_back((uint32_t)params[i].min_ingress_nodes);
         j.thr.push_back(params[i].prune_stake_threshold);
         j.frac.push_back(params[i].fraction_to_fail);
+        j.fanouts.push_back((uint32_t)params[i].gossip_push_fanout);
       }
+      if (j.slot_fanouts) j.cfg.push_fanout = *std::max_element(j.fanouts.begin(), j.fanouts.end());
       jobs.push_back(std::move(j));
     }
+  }
+  if (!c.engine_plan.empty()) {  // (before any engine exists; also with --replay-results)
+    FILE* f = std::fopen(c.engine_plan.c_str(), "w");
+    if (!f) die(1, "cannot write " + c.engine_plan);
+    for (const Job& j : jobs) {
+      std::fprintf(f, "device %d sims ", j.device);
+      for (size_t k = 0; k < j.sims.size(); ++k) std::fprintf(f, "%s%zu", k ? "," : "", j.sims[k]);
+      std::fprintf(f, " active-set-size %u fanouts ", j.cfg.active_set_size);
+      for (size_t k = 0; k < j.fanouts.size(); ++k) std::fprintf(f, "%s%u", k ? "," : "", j.fanouts[k]);
+      std::fprintf(f, "\n");
+    }
+    std::fclose(f);
+  }
+
+  std::vector<gsrep::SimArrays> sims(num_sims);
+  if (!c.replay_results.empty()) {
+    std::string err;
+    if (!gsrep::load_results(c.replay_results, sims, err)) die(1, err);
+    if (sims.size() != num_sims) die(1, "results file holds " + std::to_string(sims.size()) + " simulations, not " +
+                                            std::to_string(num_sims));
+  } else if (num_sims) {
     for (size_t i = 0; i < num_sims; ++i)
       gsrep::log_info(stderr, TMAIN, "##### SIMULATION ITERATION: " + std::to_string(i) + " #####");
     // one worker thread per requested device; workers beyond the visible devices share

@@ -70,6 +70,7 @@ struct BinArgs {
   uint32_t N, ASZ, fanout, fc, capin, Gmax, PW, BS, nbins, ORW, csr_cap, qmin;
   size_t PAIRS, pool_bin_cap;  // pool region of a bin: 2^BS * capin records (in-degrees are <= capin)
   int record;
+  const uint32_t* sfan;  // [S] per-slot fanouts while they differ, else null (every slot takes `fanout`)
 };
 
 // bins dealt to XCDs in contiguous ranges (workgroup i runs on XCD i % 8)
@@ -102,12 +103,13 @@ struct RecN {
 };
 
 // The pushes of frontier pair p (gossip.rs:511-541): ring slots taken this round.
-template <int ASZP>
+template <int ASZP, bool PF>  // PF: per-slot fanouts (a.sfan)
 __device__ inline uint32_t pair_pushes(const BinArgs& a, uint32_t p, uint32_t (&row)[ASZP], uint32_t& o,
                                        uint32_t& u) {
   o = p / a.N;
   u = p - o * a.N;
   const uint32_t org = a.origin[o], nf = a.nfail[o], ob = a.obkt[o];
+  const uint32_t fan = PF ? a.sfan[o] : a.fanout;
   const uint32_t* orow = a.own + (size_t)u * a.ORW;
   load_row<ASZP>(orow, row);
   const uint32_t meta = orow[ASZP];
@@ -117,7 +119,7 @@ __device__ inline uint32_t pair_pushes(const BinArgs& a, uint32_t p, uint32_t (&
     hv = a.hl[ent];
     load_row<ASZP>(a.peers + (size_t)ent * ASZP, row);
   }
-  uint32_t pushm = taken_slots<ASZP>(row, hv & 0xFF, hv >> 8, a.ASZ, a.mask[p], org, a.fanout);
+  uint32_t pushm = taken_slots<ASZP>(row, hv & 0xFF, hv >> 8, a.ASZ, a.mask[p], org, fan);
   if (nf) {  // failed peers burn their fanout slot (gossip.rs:538-541)
 #pragma unroll
     for (int s = 0; s < ASZP; ++s)
@@ -163,7 +165,7 @@ constexpr uint32_t BIN_MIN_FRONTIER = 1u << 17;
 
 // WG: run by the single-workgroup kernel (k_bin_small): its atomics are workgroup scope
 // (executed in the XCD's L2, atomic_or_wg); the grid-wide expand's are device scope.
-template <int ASZP, bool WG = false>
+template <int ASZP, bool PF, bool WG = false>
 __device__ inline void bin_direct(const BinArgs& a, uint32_t d, uint32_t qn, const uint32_t* __restrict__ qcur,
                                   uint32_t* __restrict__ qnxt) {
   const uint32_t rec_hop = (d + 1) << 24;
@@ -176,7 +178,7 @@ __device__ inline void bin_direct(const BinArgs& a, uint32_t d, uint32_t qn, con
     if (i < qn) {
       uint32_t p = qcur[i];
       if (GS_OOB(p, a.PAIRS, a.err, "direct frontier pair")) p = 0;
-      pm = pair_pushes<ASZP>(a, p, row, o, u);
+      pm = pair_pushes<ASZP, PF>(a, p, row, o, u);
       const uint32_t eg = __popc(pm);
       a.egress[p] = (uint8_t)eg;
       if (a.record && eg) a.egress_acc[p] += eg;
@@ -231,7 +233,7 @@ enum : uint32_t { BIN_POLL = 0, BIN_HEAD = 1, BIN_TAIL = 2 };
 // expand/apply pairs of the predicted loop; BIN_TAIL from level dpair[pi] to the end of
 // the BFS whatever the sizes (correct for any level, fast for the small tail), publishing
 // the round's level profile (hprof) for the host's next prediction.
-template <int ASZP>
+template <int ASZP, bool PF>
 __global__ __launch_bounds__(BIN_ST) void k_bin_small(BinArgs a, uint32_t mode, uint32_t d0, uint32_t pi, uint32_t lim,
                                                      uint32_t* __restrict__ q0, uint32_t* __restrict__ q1,
                                                      uint32_t* __restrict__ hstate, uint32_t seq) {
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(BIN_ST) void k_bin_small(BinArgs a, uint32_t mode, 
   uint32_t qn = s_qn;
   while (qn > 0 && qn <= lim && d < 254) {
     if (threadIdx.x == 0 && mode == BIN_POLL) __hip_atomic_store(&a.hlvl[d], qn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    bin_direct<ASZP, true>(a, d, qn, (d & 1) ? q1 : q0, (d & 1) ? q0 : q1);
+    bin_direct<ASZP, PF, true>(a, d, qn, (d & 1) ? q1 : q0, (d & 1) ? q0 : q1);
     __syncthreads();
     if (threadIdx.x == 0) s_qn = __hip_atomic_load(&a.lvl[d + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
@@ -273,7 +275,7 @@ __global__ __launch_bounds__(BIN_ST) void k_bin_small(BinArgs a, uint32_t mode, 
 // entries there when the BFS already ended). A level below qmin, or any level when no
 // apply follows (binned == 0), runs the direct path here; pair pi then records its next
 // level in dpair[pi + 1] (the apply does when it runs).
-template <int ASZP, class R>
+template <int ASZP, class R, bool PF>
 __global__ __launch_bounds__(512) void k_bin_expand(BinArgs a, uint32_t d, uint32_t pi, uint32_t binned,
                                                     uint32_t* __restrict__ q0, uint32_t* __restrict__ q1) {
   using RT = typename R::T;
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(512) void k_bin_expand(BinArgs a, uint32_t d, uint3
     __hip_atomic_store(&a.hlvl[d], qn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (qn < a.qmin || !binned) {
     if (pi != BIN_NOPAIR && blockIdx.x == 0 && threadIdx.x == 0) a.dpair[pi + 1] = qn ? d + 1 : d;
-    bin_direct<ASZP>(a, d, qn, qcur, qnxt);
+    bin_direct<ASZP, PF>(a, d, qn, qcur, qnxt);
     return;
   }
   const uint32_t G = (qn + a.PW - 1) / a.PW;
@@ -307,7 +309,7 @@ __global__ __launch_bounds__(512) void k_bin_expand(BinArgs a, uint32_t d, uint3
         uint32_t p = qcur[i];
         if (GS_OOB(p, a.PAIRS, a.err, "binned frontier pair")) p = 0;
         uint32_t o, u;
-        pm[j] = pair_pushes<ASZP>(a, p, row[j], o, u);
+        pm[j] = pair_pushes<ASZP, PF>(a, p, row[j], o, u);
         const uint32_t eg = __popc(pm[j]);
         a.egress[p] = (uint8_t)eg;
         if (a.record && eg) a.egress_acc[p] += eg;
@@ -810,7 +812,7 @@ bool bin_supported(const BinGeom& g, uint32_t fcap) {
   return g.T_words * 4 <= (1ull << 30) && bin_expand_lds_bytes(g.nbins, g.PW, fcap, g.narrow ? 4 : 8) <= 160 * 1024;
 }
 
-template <class R>
+template <class R, bool PF>  // PF: the slots' fanouts differ (a.sfan); the uniform kernels are unchanged by it
 static hipError_t run_binned(Engine& e, BinArgs& a) {
   hipError_t r;
   const size_t lds_x = bin_expand_lds_bytes(a.nbins, a.PW, a.fc, sizeof(typename R::T));
@@ -832,7 +834,7 @@ static hipError_t run_binned(Engine& e, BinArgs& a) {
   if ((r = hipFuncSetAttribute((const void*)k_bin_gather<R, GATHER_THREADS_L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g)))
     return r;
   GS_ASZP_DISPATCH(e.ASZP, {
-    r = hipFuncSetAttribute((const void*)k_bin_expand<A, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
+    r = hipFuncSetAttribute((const void*)k_bin_expand<A, R, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
   });
   if (r != hipSuccess) return r;
   // Levels of at most `lim` frontier pairs run in one workgroup (k_bin_small); larger ones
@@ -875,7 +877,7 @@ static hipError_t run_binned(Engine& e, BinArgs& a) {
     uint32_t k1 = (uint32_t)pv.size();  // one past the last level above the tail threshold
     while (k1 > k0 && pv[k1 - 1] <= std::min(tail_thr, lim)) --k1;
     const uint32_t npairs = std::min<uint32_t>(k1 - k0 + mv_margin(), 250);
-    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_small<A>), dim3(1), dim3(BIN_ST), 0, e.st, a, BIN_HEAD, 0u, 0u,
+    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_small<A, PF>), dim3(1), dim3(BIN_ST), 0, e.st, a, BIN_HEAD, 0u, 0u,
                                                 lim, e.q[0], e.q[1], e.mv_hstate_dev, 0u));
     // GS_FLAG_MISPREDICT_LEVELS (tests): every other round inverts the predicted binned /
     // direct choice of each pair, so real levels of >= qmin pairs run direct while the
@@ -883,7 +885,7 @@ static hipError_t run_binned(Engine& e, BinArgs& a) {
     const uint32_t flip = (e.prm.flags & GS_FLAG_MISPREDICT_LEVELS) ? (e.mv_seq & 1u) : 0u;
     for (uint32_t i = 0; i < npairs; ++i) {
       const uint32_t binned = (k0 + i < pv.size() && pv[k0 + i] >= a.qmin ? 1u : 0u) ^ flip;  // predicted binned level
-      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_expand<A, R>), dim3(xgrid), dim3(xth), lds_x, e.st, a, 0u, i,
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_expand<A, R, PF>), dim3(xgrid), dim3(xth), lds_x, e.st, a, 0u, i,
                                                   binned, e.q[0], e.q[1]));
       if (binned) {
         if (SBA) hipLaunchKernelGGL(k_bin_apply_sb, dim3(sbgrid), dim3(APPLY_THREADS), lds_sb, e.st, a, 0u, i, e.q[0], e.q[1]);
@@ -891,13 +893,13 @@ static hipError_t run_binned(Engine& e, BinArgs& a) {
       }
     }
     const uint32_t seq = ++e.mv_seq ? e.mv_seq : ++e.mv_seq;
-    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_small<A>), dim3(1), dim3(BIN_ST), 0, e.st, a, BIN_TAIL, 0u, npairs,
+    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_small<A, PF>), dim3(1), dim3(BIN_ST), 0, e.st, a, BIN_TAIL, 0u, npairs,
                                                 lim, e.q[0], e.q[1], e.mv_hstate_dev, seq));
   } else {
     uint32_t d = 0, nlev = 0;
     for (;;) {
       hs[0] = MV_PENDING;
-      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_small<A>), dim3(1), dim3(BIN_ST), 0, e.st, a, BIN_POLL, d, 0u,
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_small<A, PF>), dim3(1), dim3(BIN_ST), 0, e.st, a, BIN_POLL, d, 0u,
                                                   lim, e.q[0], e.q[1], e.mv_hstate_dev, 0u));
       e.bfs_level = d;
       if ((r = mv_wait(hs, e.st, d))) return r;
@@ -914,7 +916,7 @@ static hipError_t run_binned(Engine& e, BinArgs& a) {
           break;
         }
         hl[d] = MV_PENDING;
-        GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_expand<A, R>), dim3(xgrid), dim3(xth), lds_x, e.st, a, d,
+        GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_bin_expand<A, R, PF>), dim3(xgrid), dim3(xth), lds_x, e.st, a, d,
                                                     BIN_NOPAIR, 1u, e.q[0], e.q[1]));
         if (SBA) hipLaunchKernelGGL(k_bin_apply_sb, dim3(sbgrid), dim3(APPLY_THREADS), lds_sb, e.st, a, d, BIN_NOPAIR, e.q[0], e.q[1]);
         else hipLaunchKernelGGL(k_bin_apply<R>, dim3(bgrid), dim3(APPLY_THREADS), lds_a, e.st, a, d, BIN_NOPAIR, e.q[0], e.q[1]);
@@ -947,7 +949,7 @@ hipError_t launch_bfs_binned(Engine& e, bool record) {
   a.egress = e.egress; a.egress_acc = e.egress_acc; a.lvl = e.lvl; a.err = e.err; a.area = e.bin_area;
   a.T = e.bin_T; a.pool = e.bin_pool; a.Lt = e.bin_Lt; a.binoff = e.bin_binoff;
   a.visbm = e.bin_vis; a.hlvl = e.mv_hlvl_dev; a.dpair = e.mv_dpair; a.hprof = e.mv_prof_dev;
-  a.N = e.N; a.ASZ = e.ASZ; a.fanout = e.fanout; a.fc = e.fcap; a.capin = e.capin; a.Gmax = e.bin.Gmax;
+  a.N = e.N; a.ASZ = e.ASZ; a.fanout = e.fanout; a.sfan = e.fvar ? e.sfan : nullptr; a.fc = e.fcap; a.capin = e.capin; a.Gmax = e.bin.Gmax;
   a.PW = e.bin.PW; a.BS = e.bin.BS; a.nbins = e.bin.nbins; a.ORW = e.ORW; a.csr_cap = e.bin.csr_cap;
   a.qmin = (e.prm.flags & GS_FLAG_BINNED_ALL_LEVELS) ? 1u : BIN_MIN_FRONTIER;
   if (e.prm.flags & GS_FLAG_NARROW_WAVE_PATH) a.csr_cap = 256;  // small tests reach the gather's direct placement
@@ -959,7 +961,8 @@ hipError_t launch_bfs_binned(Engine& e, bool record) {
   if ((r = hipMemsetAsync(e.bin_binoff, 0, (size_t)e.bin.nbins * 4, e.st)) != hipSuccess) return r;
   if ((r = hipMemsetAsync(e.bin_vis, 0, (e.PAIRS + 31) / 32 * 4, e.st)) != hipSuccess) return r;
   hipLaunchKernelGGL(k_bin_seed, dim3((e.S + 255) / 256), dim3(256), 0, e.st, a, e.origin, e.S, e.q[0]);
-  return e.bin.narrow ? run_binned<RecN>(e, a) : run_binned<RecW>(e, a);
+  if (a.sfan) return e.bin.narrow ? run_binned<RecN, true>(e, a) : run_binned<RecW, true>(e, a);
+  return e.bin.narrow ? run_binned<RecN, false>(e, a) : run_binned<RecW, false>(e, a);
 }
 
 }  // namespace gs

@@ -93,14 +93,14 @@ __device__ inline bool hb_part(const uint32_t* gt, uint32_t u, uint32_t M, uint3
 // frontier entry would be at any level; the pushes become area records src | node-in-bin
 // << UB | slot mask << (UB + BSC), binned by coarse destination bin (a run per row at the
 // fixed place row * XT * ASZ: an entry pushes to at most ASZ distinct peers).
-template <int ASZP, uint32_t XT>
+template <int ASZP, uint32_t XT, bool PF>
 __global__ __launch_bounds__(XT) void k_hb_graph(MvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ MvSlots S;
   __shared__ uint32_t gt[GT_WORDS];
   const uint32_t tid = threadIdx.x, nb = a.nbc, BSC = a.BSC, UB = a.UB, BPm = (1u << BSC) - 1;
   const uint32_t gm = a.Sg >= 32 ? 0xFFFFFFFFu : (1u << a.Sg) - 1u;
-  mv_slots_load(a, S, tid, XT);
+  mv_slots_load<PF>(a, S, tid, XT);
   for (uint32_t i = tid; i < GT_WORDS; i += XT) gt[i] = a.gt[i];
   uint32_t* hist = reinterpret_cast<uint32_t*>(smem);  // [nb] + scan words
   unsigned long long* stage = reinterpret_cast<unsigned long long*>(smem + mv_hist_bytes(nb));  // [XT * ASZP]
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(XT) void k_hb_graph(MvArgs a) {
 #pragma unroll
       for (int s = 0; s < ASZP; ++s) { row[s] = 0; acc[s] = 0; }
       uint2 ent;
-      if (valid && hb_part(gt, u0, gm, bu, it, ent)) mv_expand_entry<ASZP, true>(a, ent, S, row, acc, u);
+      if (valid && hb_part(gt, u0, gm, bu, it, ent)) mv_expand_entry<ASZP, true, PF>(a, ent, S, row, acc, u);
       uint32_t rk[ASZP];
 #pragma unroll
       for (int s = 0; s < ASZP; ++s) rk[s] = acc[s] ? atomicAdd(&hist[row[s] >> BSC], 1u) : 0u;
@@ -268,13 +268,13 @@ __global__ __launch_bounds__(HB_CT) void k_hb_csr(MvArgs a) {
 // push graph); per pushed-to peer the atomicOr on its visited mask returns the slots it
 // reaches first, whose distance bytes become d + 1 and whose bits go to F_{d+1}. Returns
 // the next-level entries.
-template <int ASZP, bool WG>
+template <int ASZP, bool WG, bool PF>
 __device__ inline uint32_t hb_td_entry(const MvArgs& a, uint2 ent, const MvSlots& S, const uint32_t* gt, uint32_t d,
                                        uint32_t (&row)[ASZP], uint32_t (&nwm)[ASZP], uint32_t (&bw)[ASZP]) {
   uint32_t acc[ASZP], u = 0;
 #pragma unroll
   for (int s = 0; s < ASZP; ++s) { row[s] = 0; acc[s] = 0; }
-  mv_expand_entry<ASZP, false>(a, ent, S, row, acc, u);
+  mv_expand_entry<ASZP, false, PF>(a, ent, S, row, acc, u);
   uint32_t old[ASZP];
 #pragma unroll
   for (int s = 0; s < ASZP; ++s)
@@ -304,7 +304,7 @@ __device__ inline uint32_t hb_td_entry(const MvArgs& a, uint2 ent, const MvSlots
 // while small. Every mode reports (level, entries) where it stopped in hstate. Entries are
 // written to the global queue too (the level kernels and F's clearing read them there), and
 // each level first clears F_{d-1} at its entries (level d - 1's first arrivals).
-template <int ASZP>
+template <int ASZP, bool PF>
 __global__ __launch_bounds__(HB_ST) void k_hb_small(MvArgs a, uint32_t mode, uint32_t d0, uint32_t pi,
                                                     uint2* __restrict__ q0, uint2* __restrict__ q1,
                                                     uint32_t* __restrict__ hstate, const uint2* __restrict__ seeds,
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(HB_ST) void k_hb_small(MvArgs a, uint32_t mode, uin
   __shared__ MvSlots S;
   __shared__ uint32_t gt[GT_WORDS], cnt_s;
   const uint32_t tid = threadIdx.x;
-  mv_slots_load(a, S, tid, HB_ST);
+  mv_slots_load<PF>(a, S, tid, HB_ST);
   for (uint32_t i = tid; i < GT_WORDS; i += HB_ST) gt[i] = a.gt[i];
   uint32_t d = mode == HB_TAIL ? a.dpair[pi] : d0;
   bool inL = false;     // level d's entries [0, HB_SQ) are in qL[d & 1]
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(HB_ST) void k_hb_small(MvArgs a, uint32_t mode, uin
 #pragma unroll
       for (int s = 0; s < ASZP; ++s) { row[s] = 0; nwm[s] = 0; bw[s] = 0; }
       uint32_t n = 0;
-      if (i < qn) n = hb_td_entry<ASZP, true>(a, inL && i < HB_SQ ? ql[i] : qg[i], S, gt, d, row, nwm, bw);
+      if (i < qn) n = hb_td_entry<ASZP, true, PF>(a, inL && i < HB_SQ ? ql[i] : qg[i], S, gt, d, row, nwm, bw);
       if (n) {
         const uint32_t base = atomicAdd(&cnt_s, n);
         if ((size_t)base + n <= a.q_cap) {
@@ -430,7 +430,7 @@ __device__ inline uint32_t hb_wave_reserve(const MvArgs& a, uint32_t d, uint32_t
 }
 
 // A top-down level over the chip: 64-entry chunks dealt over every wave.
-template <int ASZP>
+template <int ASZP, bool PF>
 __global__ __launch_bounds__(HB_LT) void k_hb_td(MvArgs a, uint32_t d, uint32_t pi, uint2* __restrict__ q0,
                                                  uint2* __restrict__ q1) {
   __shared__ MvSlots S;
@@ -441,7 +441,7 @@ __global__ __launch_bounds__(HB_LT) void k_hb_td(MvArgs a, uint32_t d, uint32_t 
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t nwv = gridDim.x * (HB_LT / 64), gw = blockIdx.x * (HB_LT / 64) + (tid >> 6);
   if ((size_t)blockIdx.x * HB_LT >= qn) return;  // (workgroups beyond the level leave before any setup)
-  mv_slots_load(a, S, tid, HB_LT);
+  mv_slots_load<PF>(a, S, tid, HB_LT);
   for (uint32_t i = tid; i < GT_WORDS; i += HB_LT) gt[i] = a.gt[i];
   __syncthreads();
   const uint2* qc = (d & 1) ? q1 : q0;
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(HB_LT) void k_hb_td(MvArgs a, uint32_t d, uint32_t 
 #pragma unroll
     for (int s = 0; s < ASZP; ++s) { row[s] = 0; nwm[s] = 0; bw[s] = 0; }
     uint32_t n = 0;
-    if (i < qn) n = hb_td_entry<ASZP, false>(a, qc[i], S, gt, d, row, nwm, bw);
+    if (i < qn) n = hb_td_entry<ASZP, false, PF>(a, qc[i], S, gt, d, row, nwm, bw);
     bool ok;
     uint32_t pos = hb_wave_reserve(a, d, n, ok);
     if (ok && n) {
@@ -701,15 +701,25 @@ static void hb_launch_level(Engine& e, const MvArgs& a, bool bu, uint32_t d, uin
     const uint32_t gclr = std::min<uint32_t>(2048, (e.N / 4 + HB_LT * 16 - 1) / (HB_LT * 16));
     const uint32_t grid = std::max<uint32_t>(
         std::max<uint32_t>(1, gclr), std::min<uint32_t>((std::max<uint32_t>(pred, 1) * 2 + HB_LT - 1) / HB_LT, 8192));
-    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL(k_hb_td<A>, dim3(grid), dim3(HB_LT), 0, e.st, a, d, pi, e.mv_q[0],
-                                                  e.mv_q[1]));
+    if (a.sfan) {  // the slots' fanouts differ: the PF kernels
+      GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_hb_td<A, true>), dim3(grid), dim3(HB_LT), 0, e.st, a, d, pi,
+                                                    e.mv_q[0], e.mv_q[1]));
+    } else {
+      GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_hb_td<A, false>), dim3(grid), dim3(HB_LT), 0, e.st, a, d, pi,
+                                                    e.mv_q[0], e.mv_q[1]));
+    }
   }
 }
 
 static void hb_launch_small(Engine& e, const MvArgs& a, uint32_t mode, uint32_t d0, uint32_t pi, const uint2* seeds,
                             uint32_t nseed, uint32_t seq) {
-  GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL(k_hb_small<A>, dim3(1), dim3(HB_ST), 0, e.st, a, mode, d0, pi,
-                                                e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
+  if (a.sfan) {
+    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_hb_small<A, true>), dim3(1), dim3(HB_ST), 0, e.st, a, mode, d0, pi,
+                                                  e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
+  } else {
+    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_hb_small<A, false>), dim3(1), dim3(HB_ST), 0, e.st, a, mode, d0, pi,
+                                                  e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
+  }
 }
 
 hipError_t launch_bfs_hybrid(Engine& e, bool record) {
@@ -719,10 +729,12 @@ hipError_t launch_bfs_hybrid(Engine& e, bool record) {
   const size_t lds_c = hb_csr_lds_bytes(g.BSC);
   if (!e.mv_attr_set) {
     GS_ASZP_DISPATCH(e.ASZP, {
-      r = g.XT == MV_XT_L ? hipFuncSetAttribute((const void*)k_hb_graph<A, MV_XT_L>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x)
-                          : hipFuncSetAttribute((const void*)k_hb_graph<A, MV_XT>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
+      const bool wide = g.XT == MV_XT_L;  // (both fanout forms: uniform and per slot)
+      r = hipFuncSetAttribute(wide ? (const void*)k_hb_graph<A, MV_XT_L, false> : (const void*)k_hb_graph<A, MV_XT, false>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
+      if (r == hipSuccess)
+        r = hipFuncSetAttribute(wide ? (const void*)k_hb_graph<A, MV_XT_L, true> : (const void*)k_hb_graph<A, MV_XT, true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
     });
     if (r != hipSuccess) return r;
     if ((r = hipFuncSetAttribute((const void*)k_hb_csr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c)))
@@ -758,9 +770,17 @@ hipError_t launch_bfs_hybrid(Engine& e, bool record) {
     // 1. the push graph (also the round's visited masks and distances)
     const uint32_t xgrid = std::min<uint32_t>(e.hb_slices, 4096);
     if (g.XT == MV_XT_L) {
-      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_hb_graph<A, MV_XT_L>), dim3(xgrid), dim3(MV_XT_L), lds_x, e.st, a));
+      if (a.sfan) {
+        GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_hb_graph<A, MV_XT_L, true>), dim3(xgrid), dim3(MV_XT_L), lds_x,
+                                                    e.st, a));
+      } else {
+        GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_hb_graph<A, MV_XT_L, false>), dim3(xgrid), dim3(MV_XT_L), lds_x,
+                                                    e.st, a));
+      }
+    } else if (a.sfan) {
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_hb_graph<A, MV_XT, true>), dim3(xgrid), dim3(MV_XT), lds_x, e.st, a));
     } else {
-      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_hb_graph<A, MV_XT>), dim3(xgrid), dim3(MV_XT), lds_x, e.st, a));
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_hb_graph<A, MV_XT, false>), dim3(xgrid), dim3(MV_XT), lds_x, e.st, a));
     }
     hipLaunchKernelGGL(k_hb_csr, dim3(cgrid), dim3(HB_CT), lds_c, e.st, a);
     // 2. the levels

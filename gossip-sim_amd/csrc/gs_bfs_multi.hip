@@ -56,7 +56,7 @@ namespace {
 // the rows cost more than the records; 1,024-entry slices make 4x fewer rows (C5 BFS
 // 9.36 -> 6.95 ms per round) while at C4's 245 bins 256-entry slices stay faster (730 vs
 // 768 us).
-template <int ASZP, uint32_t XT>
+template <int ASZP, uint32_t XT, bool PF>
 __global__ __launch_bounds__(XT) void k_mv_expand(MvArgs a, uint32_t d, uint32_t pi, const uint2* __restrict__ q0,
                                                   const uint2* __restrict__ q1) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(XT) void k_mv_expand(MvArgs a, uint32_t d, uint32_t
     return;
   }
   const uint32_t tid = threadIdx.x, nb = a.nbc, BSC = a.BSC, UB = a.UB, BPm = (1u << BSC) - 1;
-  mv_slots_load(a, S, tid, XT);
+  mv_slots_load<PF>(a, S, tid, XT);
   uint32_t* hist = reinterpret_cast<uint32_t*>(smem);  // [nb] + scan words
   unsigned long long* stage = reinterpret_cast<unsigned long long*>(smem + mv_hist_bytes(nb));  // [XT * ASZP]
   for (uint32_t w = blockIdx.x; w < G; w += gridDim.x) {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(XT) void k_mv_expand(MvArgs a, uint32_t d, uint32_t
 #pragma unroll
     for (int s = 0; s < ASZP; ++s) { row[s] = 0; acc[s] = 0; }
     const uint32_t i = w * XT + tid;
-    if (i < qn) mv_expand_entry<ASZP>(a, qcur[i], S, row, acc, u);
+    if (i < qn) mv_expand_entry<ASZP, true, PF>(a, qcur[i], S, row, acc, u);
     // every LDS atomic after every load: each record's rank within its coarse bin
     uint32_t rk[ASZP];
 #pragma unroll
@@ -302,7 +302,7 @@ enum : uint32_t { MV_HEAD = 0, MV_TAIL = 1, MV_POLL = 2 };  // small-kernel mode
 //            to host-mapped memory (hprof) for the next round's prediction;
 //   MV_POLL  from level d0 while levels have at most a.small entries (the polled loop).
 // Every mode reports (level, entries) where it stopped in hstate.
-template <int ASZP>
+template <int ASZP, bool PF>
 __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uint32_t d0, uint32_t pi,
                                                     uint2* __restrict__ q0, uint2* __restrict__ q1,
                                                     uint32_t* __restrict__ hstate, const uint2* __restrict__ seeds,
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uin
   __shared__ uint32_t gt[GT_WORDS], cnt_s;
   const uint32_t tid = threadIdx.x;
   const bool LP = a.fno <= MV_SMALL_LP;  // (uniform; beyond, device-scope atomics on a.pused)
-  mv_slots_load(a, S, tid, MV_ST);
+  mv_slots_load<PF>(a, S, tid, MV_ST);
   for (uint32_t i = tid; i < GT_WORDS; i += MV_ST) gt[i] = a.gt[i];
   uint32_t d = mode == MV_TAIL ? a.dpair[pi] : d0;
   bool inL = false;  // the current level's entries [0, MV_SQ) are in qL[d & 1]
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uin
       uint32_t row[ASZP], acc[ASZP], u = 0;
 #pragma unroll
       for (int s = 0; s < ASZP; ++s) { row[s] = 0; acc[s] = 0; }
-      if (i < qn) mv_expand_entry<ASZP>(a, inL && i < MV_SQ ? ql[i] : qg[i], S, row, acc, u);
+      if (i < qn) mv_expand_entry<ASZP, true, PF>(a, inL && i < MV_SQ ? ql[i] : qg[i], S, row, acc, u);
       if (a.pclk && i0 == 0) {  // (profiling only: wait for the entry's loads)
         uint32_t x = 0;
 #pragma unroll
@@ -1046,7 +1046,13 @@ void mv_geometry(uint32_t N, uint32_t S, uint32_t ASZ, uint32_t ASZP, MvGeom& g)
   g.XT = g.nbc >= MV_XT_WIDE && mv_hist_bytes(g.nbc) + (size_t)MV_XT_L * ASZP * 8 <= 160 * 1024 ? MV_XT_L : MV_XT;
   g.rows_cap = (g.q_cap + g.XT - 1) / g.XT + 1;
   g.area_cap = std::min<size_t>(g.rows_cap * g.XT * ASZ, 0xFFFFFFF0u);  // expand slice w's run at w * XT * ASZ
-  const size_t rpn = (size_t)ASZ * std::min<size_t>(sg, 4) + 16;  // pool records per node (average over a bin)
+  size_t rpn = (size_t)ASZ * std::min<size_t>(sg, 4) + 16;  // pool records per node (average over a bin)
+  // A record carries at least one slot's push, and a (slot, node) receives at most the inbound
+  // capacity (64 by default), so 64 * sg records per node cannot overflow. Networks small enough
+  // that such a pool stays below 8 MiB take it: on a few hundred nodes a group of distinct
+  // origins shares few records (the small-level kernel makes one entry, and so one record per
+  // peer, per first arrival of a node's slots), and the average above does not hold.
+  if ((size_t)N * (64 * sg + 16) * 8 <= ((size_t)8 << 20)) rpn = std::max<size_t>(rpn, 64 * sg + 16);
   g.pcap = ((size_t)1 << g.BSF) * rpn;
   // (slack: k_mv_gather reads masks up to 31 records past a node's list, the fused
   // consume's filters up to 3)
@@ -1141,6 +1147,7 @@ MvArgs mv_args(Engine& e, const MvGroup& gr, uint32_t g) {
   a.hops = e.hops; a.cnt = e.cnt; a.inb = e.inb; a.egress = e.egress; a.err = e.err;
   a.vis = e.mv_vis; a.lvl = e.lvl; a.hlvl = e.mv_hlvl_dev; a.T = e.mv_T; a.area = e.mv_area; a.ctr = e.mv_ctr;
   a.dpair = e.mv_dpair; a.hprof = nullptr; a.clear_vis = 0;
+  a.sfan = e.fvar ? e.sfan : nullptr;
   a.pool = e.mv_pool; a.pused = e.mv_pused;
   a.N = e.N; a.SP = e.SP; a.ASZ = e.ASZ; a.fanout = e.fanout; a.capin = e.capin; a.s0 = gr.s0; a.Sg = gr.sg;
   a.UB = e.mv.UB; a.BSC = e.mv.BSC; a.BSF = e.mv.BSF; a.nbc = e.mv.nbc; a.nbf = e.mv.nbf; a.TW = e.mv.TW;
@@ -1209,20 +1216,34 @@ hipError_t level_empty(Engine& e, uint32_t d, bool& empty) {
 
 // One expand launch (slices of e.mv.XT entries).
 static void launch_expand(Engine& e, const MvArgs& a, uint32_t d, uint32_t pi, size_t lds_x, uint32_t xgrid) {
+  // (a.sfan: the slots' fanouts differ -- the PF kernels; the uniform ones are unchanged by them)
   if (e.mv.XT == MV_XT_L) {
-    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT_L>), dim3(xgrid), dim3(MV_XT_L), lds_x, e.st, a,
+    if (a.sfan) {
+      GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT_L, true>), dim3(xgrid), dim3(MV_XT_L), lds_x,
+                                                    e.st, a, d, pi, e.mv_q[0], e.mv_q[1]));
+    } else {
+      GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT_L, false>), dim3(xgrid), dim3(MV_XT_L), lds_x,
+                                                    e.st, a, d, pi, e.mv_q[0], e.mv_q[1]));
+    }
+  } else if (a.sfan) {
+    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT, true>), dim3(xgrid), dim3(MV_XT), lds_x, e.st, a,
                                                   d, pi, e.mv_q[0], e.mv_q[1]));
   } else {
-    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT>), dim3(xgrid), dim3(MV_XT), lds_x, e.st, a, d,
-                                                  pi, e.mv_q[0], e.mv_q[1]));
+    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT, false>), dim3(xgrid), dim3(MV_XT), lds_x, e.st, a,
+                                                  d, pi, e.mv_q[0], e.mv_q[1]));
   }
 }
 
 // The small-level kernel (one workgroup, k_mv_small).
 static void launch_small_levels(Engine& e, const MvArgs& a, uint32_t mode, uint32_t d0, uint32_t pi,
                                 const uint2* seeds, uint32_t nseed, uint32_t seq, size_t lds_s) {
-  GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_small<A>), dim3(1), dim3(MV_ST), lds_s, e.st, a, mode, d0, pi,
-                                                e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
+  if (a.sfan) {
+    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_small<A, true>), dim3(1), dim3(MV_ST), lds_s, e.st, a, mode, d0,
+                                                  pi, e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
+  } else {
+    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_small<A, false>), dim3(1), dim3(MV_ST), lds_s, e.st, a, mode, d0,
+                                                  pi, e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
+  }
 }
 
 // The level loop of one slot group. Two forms:
@@ -1288,11 +1309,12 @@ static hipError_t mv_attrs(Engine& e) {
   const size_t lds_s = fno <= MV_SMALL_LP ? (size_t)fno * 4 : 0;
   if (!e.mv_attr_set) {
     GS_ASZP_DISPATCH(e.ASZP, {
-      r = e.mv.XT == MV_XT_L
-              ? hipFuncSetAttribute((const void*)k_mv_expand<A, MV_XT_L>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_x)
-              : hipFuncSetAttribute((const void*)k_mv_expand<A, MV_XT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_x);
+      const bool wide = e.mv.XT == MV_XT_L;  // (both fanout forms: uniform and per slot)
+      r = hipFuncSetAttribute(wide ? (const void*)k_mv_expand<A, MV_XT_L, false> : (const void*)k_mv_expand<A, MV_XT, false>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
+      if (r == hipSuccess)
+        r = hipFuncSetAttribute(wide ? (const void*)k_mv_expand<A, MV_XT_L, true> : (const void*)k_mv_expand<A, MV_XT, true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
     });
     if (r != hipSuccess) return r;
     if ((r = hipFuncSetAttribute((const void*)k_mv_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)))
@@ -1302,7 +1324,9 @@ static hipError_t mv_attrs(Engine& e) {
     if ((r = hipFuncSetAttribute((const void*)k_mv_consume, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g)))
       return r;
     GS_ASZP_DISPATCH(e.ASZP, {
-      r = hipFuncSetAttribute((const void*)k_mv_small<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
+      r = hipFuncSetAttribute((const void*)k_mv_small<A, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
+      if (r == hipSuccess)
+        r = hipFuncSetAttribute((const void*)k_mv_small<A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
     });
     if (r != hipSuccess) return r;
     e.mv_attr_set = true;

@@ -164,7 +164,7 @@ __device__ inline uint2 ld_entry(const uint2* p) {
 // slots in FIFO order), then failed peers burn their slot (gossip.rs:527-541); the slot's
 // egress byte. Lane j < ASZP returns ring slot j's record (its peer and the slots that push
 // to it) in row[0] / acc[0].
-template <int ASZP, uint32_t LW>
+template <int ASZP, uint32_t LW, bool PF>
 __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, const MvSlots& S, uint32_t (&row)[ASZP],
                                       uint32_t (&acc)[ASZP], uint32_t& u) {
   constexpr int TQ = (mv_orw<ASZP>() - ASZP) / 4;
@@ -199,7 +199,7 @@ __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, co
   }
   uint32_t tk = 0;
   if (inM) {
-    tk = taken_slots<ASZP>(rw, hv & 0xFF, hv >> 8, a.ASZ, pm, S.sorg[j], a.fanout);
+    tk = taken_slots<ASZP>(rw, hv & 0xFF, hv >> 8, a.ASZ, pm, S.sorg[j], PF ? S.sfan[j] : a.fanout);
     const uint32_t f = S.sfk[j];
     if (f) {  // failed peers burn their fanout slot (gossip.rs:538-541)
 #pragma unroll
@@ -221,7 +221,7 @@ __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, co
   acc[0] = ma;
 }
 
-template <int ASZP>
+template <int ASZP, bool PF>
 __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   // (everything in the dynamic LDS: no static shared memory shifts its 16-byte base)
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
   uint2* gq = p.gq + (size_t)g * p.gq_cap;
   auto node_of = [&](uint32_t li) { return ((((li >> BSF) << GL) + g) << BSF) | (li & BPm); };
 
-  mv_slots_load(a, S, tid, PB_T);
+  mv_slots_load<PF>(a, S, tid, PB_T);
   for (uint32_t i = tid; i < GT_WORDS; i += PB_T) gt[i] = a.gt[i];
   for (uint32_t i = tid; i < NO; i += PB_T) {
     visL[i] = 0;
@@ -320,9 +320,9 @@ __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
       const uint32_t i = c0 + tid;
       if (wide) {
         const uint32_t e = tid / LW;
-        pb_expand_wide<ASZP, LW>(a, e < ne ? ent[e] : make_uint2(0u, 0u), e < ne, S, row, acc, u);
+        pb_expand_wide<ASZP, LW, PF>(a, e < ne ? ent[e] : make_uint2(0u, 0u), e < ne, S, row, acc, u);
       } else if (tid < CH && i < ne) {
-        mv_expand_entry<ASZP>(a, i < PB_EC ? ent[i] : ld_entry(&gq[i - PB_EC]), S, row, acc, u);
+        mv_expand_entry<ASZP, true, PF>(a, i < PB_EC ? ent[i] : ld_entry(&gq[i - PB_EC]), S, row, acc, u);
       }
       if (trc && c0 == 0) {  // (trace: thread 0's own entry, its loads and stores drained)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -576,7 +576,11 @@ hipError_t launch_bfs_pers(Engine& e, const MvArgs& a, const MvGroup& gr) {
   hipError_t r = hipSuccess;
   if (e.pb_attr_lds != e.pb_lds) {  // (once per engine)
     GS_ASZP_DISPATCH(e.ASZP, {
-      r = hipFuncSetAttribute((const void*)k_mv_pbfs<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.pb_lds);
+      r = hipFuncSetAttribute((const void*)k_mv_pbfs<A, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)e.pb_lds);
+      if (r == hipSuccess)
+        r = hipFuncSetAttribute((const void*)k_mv_pbfs<A, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)e.pb_lds);
     });
     if (r != hipSuccess) return r;
     e.pb_attr_lds = e.pb_lds;
@@ -612,10 +616,18 @@ hipError_t launch_bfs_pers(Engine& e, const MvArgs& a, const MvGroup& gr) {
   if (twice) {
     PbArgs q = p;
     q.tr = nullptr;
-    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, q));
+    if (a.sfan) {
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A, true>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, q));
+    } else {
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A, false>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, q));
+    }
     if ((r = hipMemsetAsync(e.pb_blk, 0, PB_BLK_WORDS * 4, e.st))) return r;
   }
-  GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, p));
+  if (a.sfan) {  // the slots' fanouts differ: the PF kernel (the uniform one is unchanged by it)
+    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A, true>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, p));
+  } else {
+    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A, false>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, p));
+  }
   if (trace) {  // (diagnostics: waits for the launch; clocks at 100 MHz)
     if ((r = hipMemcpyAsync(trh, trd, sizeof(trh), hipMemcpyDeviceToHost, e.st)) || (r = hipStreamSynchronize(e.st)))
       return r;

@@ -658,6 +658,44 @@ int gs_set_slots(gs_engine* eh, const gs_slot* slots, uint32_t n_slots) {
   return GS_OK;
 }
 
+// Per-slot Config::gossip_push_fanout (the .take(fanout) of gossip.rs:527-536 is the only
+// reader): params.push_fanout stays the capacity every buffer is sized by. The kernels take
+// the per-slot array only while the values differ; equal values run the scalar path.
+int gs_set_slot_fanouts(gs_engine* eh, const uint32_t* fanout) {
+  ENGINE(eh);
+  if (int s_ = flush_rot_clear(e)) return s_;
+  std::vector<uint32_t> f(e->S, e->prm.push_fanout);
+  if (fanout) {
+    for (uint32_t o = 0; o < e->S; ++o) {
+      if (fanout[o] < 1 || fanout[o] > e->prm.push_fanout)
+        return fail(GS_EINVAL, "gs_set_slot_fanouts: slot " + std::to_string(o) + " fanout " +
+                                   std::to_string(fanout[o]) + " is outside [1, params.push_fanout = " +
+                                   std::to_string(e->prm.push_fanout) + "]");
+      f[o] = fanout[o];
+    }
+  }
+  bool var = false;
+  for (uint32_t o = 1; o < e->S; ++o) var |= f[o] != f[0];
+  if (var || e->sfan) {
+    if (!e->sfan)
+      if (int s_ = dalloc(*e, &e->sfan, e->S, 0)) return s_;
+    HIPC(hipMemcpyAsync(e->sfan, f.data(), e->S * 4, hipMemcpyHostToDevice, e->st));
+    HIPC(hipStreamSynchronize(e->st));
+  }
+  e->h_sfan = f;
+  e->fvar = var;
+  // the scalar the kernels take while the values are equal; else the longest prefix of any slot
+  e->fanout = *std::max_element(f.begin(), f.end());
+  return GS_OK;
+}
+
+int gs_get_slot_fanouts(gs_engine* eh, uint32_t* out) {
+  ENGINE(eh);
+  if (!out) return fail(GS_EINVAL, "null argument");
+  for (uint32_t o = 0; o < e->S; ++o) out[o] = e->h_sfan.empty() ? e->prm.push_fanout : e->h_sfan[o];
+  return GS_OK;
+}
+
 int gs_sync(gs_engine* eh) {
   ENGINE(eh);
   return check_err(e);
@@ -1391,7 +1429,8 @@ int gs_read_mst(gs_engine* eh, uint32_t slot, uint32_t* parent) {
   auto take_index = [&](uint32_t u, uint32_t w) -> uint32_t {
     const size_t ent = (size_t)u * NB + std::min(bkt[u], bkt[org]);
     uint32_t t = 0;
-    for (uint32_t i = 0; i < lens[ent] && t < e->fanout; ++i) {
+    const uint32_t fan = e->h_sfan.empty() ? e->fanout : e->h_sfan[slot];
+    for (uint32_t i = 0; i < lens[ent] && t < fan; ++i) {
       const uint32_t p = peers[ent * e->ASZ + i];
       if (((fifo[u] >> i) & 1u) || p == org) continue;
       if (p == w) return t;

@@ -51,7 +51,8 @@ struct Engine {
   size_t PAIRS = 0;          // S * NP
   uint32_t ASZ = 0, ASZP = 0, fanout = 0, capin = 64;
   uint32_t bfs_mode = GS_BFS_LEVEL;
-  uint32_t fcap = 0;             // min(fanout, active_set_size): pushes per node
+  uint32_t fcap = 0;             // min(params.push_fanout, active_set_size): pushes per node at most (the
+                                 // capacity; `fanout` is the slots' uniform value, or the largest of theirs)
   // (slot o, node u) strides of the prune masks and the round's egress bytes: slot-major
   // (N, 1), or node-major (1, SP) for the multi-source BFS, whose expansion reads every
   // slot's mask of a node at once (SP = slots rounded up to 4)
@@ -86,6 +87,9 @@ struct Engine {
   double* thr = nullptr;
   uint32_t* nfail = nullptr;
   uint32_t* slot_prunes = nullptr;  // prunees emitted in the current round
+  uint32_t* sfan = nullptr;         // push fanout of each slot (gs_set_slot_fanouts; `fanout` until then)
+  std::vector<uint32_t> h_sfan;     // its host copy
+  bool fvar = false;                // the slots' fanouts differ (else every slot's is `fanout`)
   // pair arrays
   uint8_t* hops = nullptr;
   uint32_t* cnt = nullptr;
@@ -186,7 +190,8 @@ struct Engine {
   uint32_t* rot_changed_b[2] = {nullptr, nullptr};
 
   size_t rwg_attr_lds = 0;          // dynamic LDS the round kernel was last configured for
-  bool rwg_attr_prof = false;       // ... and for which instantiation (phase clocks or not)
+  bool rwg_attr_prof = false;       // ... and for which instantiation (phase clocks or not,
+  bool rwg_attr_pf = false;         // per-slot fanouts or not)
   // node-range partition (gs_partition.hip): this rank owns node ids [part_lo, part_hi)
   // (= [vlo, vlo + NP)) and the fine bins [part_flo, part_flo + part_fno) of the multi BFS
   bool part_on = false;

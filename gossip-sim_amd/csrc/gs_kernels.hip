@@ -359,6 +359,7 @@ struct BfsArgs {
   int record;
   uint32_t N, S, ASZ, fanout, capin;
   size_t PAIRS;
+  const uint32_t* sfan;  // [S] per-slot fanouts while they differ, else null (every slot takes `fanout`)
 };
 
 
@@ -371,7 +372,7 @@ struct BfsArgs {
 // wave collectives. CNT/HOPS index by peer (LDS tables, or global + base).
 template <int ASZP, class QT, bool LDS_TAIL>
 __device__ inline uint32_t expand_node(const BfsArgs& a, bool valid, uint32_t u, uint32_t ob, uint32_t org,
-                                       uint32_t nf, uint32_t pmask, size_t base, uint32_t d, uint32_t* cntp,
+                                       uint32_t nf, uint32_t fan, uint32_t pmask, size_t base, uint32_t d, uint32_t* cntp,
                                        uint8_t* hopsp, QT* nxt, uint32_t* tail, size_t qoff, bool& overflow) {
   uint32_t row[ASZP];
   uint32_t pushm = 0;
@@ -381,7 +382,7 @@ __device__ inline uint32_t expand_node(const BfsArgs& a, bool valid, uint32_t u,
     const uint32_t ent = u * NB + b;
     const uint32_t hv = a.hl[ent];
     load_row<ASZP>(a.peers + (size_t)ent * ASZP, row);
-    pushm = taken_slots<ASZP>(row, hv & 0xFF, hv >> 8, a.ASZ, pmask, org, a.fanout);
+    pushm = taken_slots<ASZP>(row, hv & 0xFF, hv >> 8, a.ASZ, pmask, org, fan);
 #ifdef GS_DEBUG_BOUNDS
     for (int s = 0; s < ASZP; ++s)
       if (((pushm >> s) & 1u) && GS_OOB(row[s], a.N, a.err, "expand peer")) pushm &= ~(1u << s);
@@ -452,6 +453,7 @@ __global__ __launch_bounds__(256) void k_bfs_wg(BfsArgs a) {
     const uint32_t org = a.origin[o];
     const uint32_t ob = a.obkt[o];
     const uint32_t nf = a.nfail[o];
+    const uint32_t fan = a.sfan ? a.sfan[o] : a.fanout;
     const size_t base = (size_t)o * N;
     for (uint32_t v = tid; v < N; v += bd) { cnt_l[v] = 0; hops_l[v] = 0xFF; eg_l[v] = 0; }
     for (uint32_t i = tid; i < 256; i += bd) hist_l[i] = 0;
@@ -473,7 +475,7 @@ __global__ __launch_bounds__(256) void k_bfs_wg(BfsArgs a) {
         const uint32_t u = valid ? cur[i0 + tid] : 0;
         const uint32_t pm = valid ? a.mask[base + u] : 0;
         const uint32_t pushes =
-            expand_node<ASZP, uint16_t, true>(a, valid, u, ob, org, nf, pm, base, d, cnt_l, hops_l, nxt, &ctrl[1], 0,
+            expand_node<ASZP, uint16_t, true>(a, valid, u, ob, org, nf, fan, pm, base, d, cnt_l, hops_l, nxt, &ctrl[1], 0,
                                         overflow);
         if (valid) eg_l[u] = (uint8_t)pushes;
       }
@@ -553,8 +555,9 @@ __global__ __launch_bounds__(256) void k_bfs_level(BfsArgs a, uint32_t d, const 
     const size_t base = (size_t)o * N;
     const uint32_t org = a.origin[o];
     const uint32_t nf = a.nfail[o];
+    const uint32_t fan = a.sfan ? a.sfan[o] : a.fanout;
     const uint32_t pm = valid ? a.mask[p] : 0;
-    const uint32_t pushes = expand_node<ASZP, uint32_t, false>(a, valid, u, a.obkt[o], org, nf, pm, base, d,
+    const uint32_t pushes = expand_node<ASZP, uint32_t, false>(a, valid, u, a.obkt[o], org, nf, fan, pm, base, d,
                                                         a.cnt + base, a.hops + base, qnxt, &a.lvl[d + 1], base,
                                                         overflow);
     if (valid) {
@@ -583,6 +586,7 @@ static BfsArgs bfs_args(Engine& e) {
   a.bucket = e.bucket; a.peers = e.peers; a.hl = e.hl; a.frank = e.frank; a.origin = e.origin; a.obkt = e.obkt;
   a.nfail = e.nfail; a.mask = e.mask; a.hops = e.hops; a.cnt = e.cnt; a.inb = e.inb; a.egress = e.egress;
   a.lvl = e.lvl; a.err = e.err; a.N = e.N; a.S = e.S; a.ASZ = e.ASZ; a.fanout = e.fanout; a.capin = e.capin;
+  a.sfan = e.fvar ? e.sfan : nullptr;
   a.PAIRS = e.PAIRS;
   a.egress_acc = e.egress_acc; a.stake = e.stake; a.srank = e.srank; a.strand = e.strand; a.bm = e.bm;
   a.rs_u32 = e.rs_u32; a.rs_ssum = e.rs_ssum; a.rs_hist = e.rs_hist; a.W = e.bm_words; a.record = 0;

@@ -72,6 +72,9 @@ struct MvArgs {
   uint32_t pg_parts;          // T rows per push-graph slice (1 + the group's lower origin buckets)
   uint32_t pg_slices;         // push-graph slices (XT nodes each)
   uint32_t bu_min;            // bottom-up level: predicted entries at least (host side)
+  // per-slot fanouts [S] while they differ (the PF kernels; `fanout` is then the longest of them), else
+  // null: every slot takes `fanout`
+  const uint32_t* sfan;
 };
 
 // Entry b of expand run (T row) w: b = 0 the run's base in the record area, b = 1 + c its
@@ -130,15 +133,20 @@ __host__ __device__ inline uint32_t mv_ohash(uint32_t x) { return (x * 0x9E3779B
 // that may take the shared-prefix path (pz: all, or none when the origin hash is
 // incomplete, so that every slot takes the per-slot path), the origin -> slot-mask hash of
 // the group table, and per failure class c the slots in which a peer of class c failed
-// (fm[c] = slots j with 0 < c <= fk[j]; class 255 = fails nowhere, fm[255] = 0).
+// (fm[c] = slots j with 0 < c <= fk[j]; class 255 = fails nowhere, fm[255] = 0). With per-slot
+// fanouts (a.sfan): each slot's fanout, and per ring position i the slots with fanout > i
+// (fgt[i]: position i is inside their prefix) and with fanout == i (feq[i]: position i is
+// their stand-in when their origin sits inside their prefix).
 struct MvSlots {
   uint32_t sorg[32], sfk[32];
   uint2 otab[128];
   uint32_t fm[256];
   uint32_t pz;
+  uint32_t sfan[32], fgt[32], feq[32];
 };
 
 // (no barrier: the caller's first __syncthreads publishes S)
+template <bool PF = false>
 __device__ inline void mv_slots_load(const MvArgs& a, MvSlots& S, uint32_t tid, uint32_t nth) {
   if (tid < a.Sg) {
     S.sorg[tid] = a.origin[a.s0 + tid];
@@ -156,6 +164,19 @@ __device__ inline void mv_slots_load(const MvArgs& a, MvSlots& S, uint32_t tid, 
     S.fm[c] = m;
   }
   if (tid == 0) S.pz = a.gt[GT_OTOK] ? 0xFFFFFFFFu : 0u;
+  if constexpr (PF) {
+    if (tid < 32) S.sfan[tid] = tid < a.Sg ? a.sfan[a.s0 + tid] : 0u;
+    for (uint32_t i = tid; i < 32; i += nth) {
+      uint32_t gtm = 0, eqm = 0;
+      for (uint32_t j = 0; j < a.Sg; ++j) {
+        const uint32_t f = a.sfan[a.s0 + j];
+        gtm |= (uint32_t)(f > i) << j;
+        eqm |= (uint32_t)(f == i) << j;
+      }
+      S.fgt[i] = gtm;
+      S.feq[i] = eqm;
+    }
+  }
 }
 
 // The group's slots whose origin is node x.
@@ -183,7 +204,8 @@ constexpr int mv_orw() { return ((ASZP + 1 + ASZP / 4) + 3) & ~3; }
 // failures ran the per-slot selection -- C4's five fail-nodes slots at every entry). Only
 // slots with prune bits at u run the per-slot selection, which a wave executes for the
 // union of its lanes' slots. Plain slots' push counts come from bit-sliced counters.
-template <int ASZP, bool EG = true>  // EG: write the egress bytes of the entry's slots
+// EG: write the egress bytes of the entry's slots. PF: per-slot fanouts (a.sfan; S.sfan, S.fgt, S.feq)
+template <int ASZP, bool EG = true, bool PF = false>
 __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, const MvSlots& S, uint32_t (&row)[ASZP],
                                        uint32_t (&acc)[ASZP], uint32_t& u) {
   constexpr int TQ = (mv_orw<ASZP>() - ASZP) / 4;
@@ -248,17 +270,41 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
         pc4 ^= x;
       };
       uint32_t rem = 0;  // plain slots whose origin is in the prefix
+      if constexpr (PF) {
+        // Per-slot fanouts: the same ring prefix, of the longest fanout; ring position i
+        // belongs to the prefix of the slots fgt[i], so only those push to it, and a slot is
+        // collected only when its origin sits inside its OWN prefix. Such a slot takes
+        // position `its fanout` instead: position i for the slots feq[i].
 #pragma unroll
-      for (int s = 0; s < ASZP; ++s) {
-        if (!((tkn >> s) & 1u)) continue;
-        const uint32_t om = mv_origin_slots(S, row[s]) & plain;
-        take(s, plain & ~om);
-        rem |= om;
-      }
-      if (rem) {  // those slots take position `fanout` instead (disjoint from the prefix)
+        for (int s = 0; s < ASZP; ++s) {
+          if (!((tkn >> s) & 1u)) continue;
+          const uint32_t in = plain & S.fgt[(uint32_t)s >= head ? (uint32_t)s - head : (uint32_t)s + SZ - head];
+          const uint32_t om = mv_origin_slots(S, row[s]) & in;
+          take(s, in & ~om);
+          rem |= om;
+        }
+        if (rem) {
+          const uint32_t lm = (1u << L) - 1u, val = ((lm << head) | (lm >> (SZ - head))) & full;
 #pragma unroll
-        for (int s = 0; s < ASZP; ++s)
-          if ((nxt >> s) & 1u) take(s, rem);
+          for (int s = 0; s < ASZP; ++s) {
+            if (!((val >> s) & 1u)) continue;
+            const uint32_t x = rem & S.feq[(uint32_t)s >= head ? (uint32_t)s - head : (uint32_t)s + SZ - head];
+            if (x) take(s, x);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int s = 0; s < ASZP; ++s) {
+          if (!((tkn >> s) & 1u)) continue;
+          const uint32_t om = mv_origin_slots(S, row[s]) & plain;
+          take(s, plain & ~om);
+          rem |= om;
+        }
+        if (rem) {  // those slots take position `fanout` instead (disjoint from the prefix)
+#pragma unroll
+          for (int s = 0; s < ASZP; ++s)
+            if ((nxt >> s) & 1u) take(s, rem);
+        }
       }
     }
   }
@@ -281,7 +327,7 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
       }
       const uint32_t pm = t == 0 ? m4[q].x : t == 1 ? m4[q].y : t == 2 ? m4[q].z : m4[q].w;
       const uint32_t f = S.sfk[j];
-      uint32_t tk = taken_slots<ASZP>(row, head, len, a.ASZ, pm, S.sorg[j], a.fanout);
+      uint32_t tk = taken_slots<ASZP>(row, head, len, a.ASZ, pm, S.sorg[j], PF ? S.sfan[j] : a.fanout);
       if (f) {  // failed peers burn their fanout slot (gossip.rs:538-541)
 #pragma unroll
         for (int s = 0; s < ASZP; ++s)

@@ -112,6 +112,7 @@ struct RoundArgs {
   uint32_t N, S, ASZ, fanout, fcap;
   size_t PAIRS;
   int record;
+  const uint32_t* sfan;  // [S] per-slot fanouts while they differ (the PF kernels), else null: every slot takes `fanout`
 };
 
 // Phase clock: thread 0 adds the time since the last mark to phase_clk[ph].
@@ -663,7 +664,7 @@ __device__ void rotate_ahead_wg(const RoundArgs& a, uint32_t* lids) {
     rotate_entry<ASZP>(a.bucket, a.P, a.IX, a.rpeers, a.rhl, lids, a.rchanged, N, a.ASZ, a.seed, a.rround, gid);
 }
 
-template <int ASZP, bool OFF16, int FP, bool PROF>
+template <int ASZP, bool OFF16, int FP, bool PROF, bool PF>  // PF: per-slot fanouts (a.sfan)
 __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundArgs a) {
   using PMT = typename std::conditional<(ASZP <= 16), uint16_t, uint32_t>::type;
   using OFFT = typename std::conditional<OFF16, uint16_t, uint32_t>::type;
@@ -696,6 +697,7 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
   }
   const uint32_t o = blockIdx.x - a.rot_on;
   const uint32_t org = a.origin[o], ob = a.obkt[o], nf = a.nfail[o];
+  const uint32_t fan = PF ? a.sfan[o] : a.fanout;  // (one slot per workgroup: a scalar)
   const size_t base = (size_t)o * N;
   uint32_t errf = 0;
   unsigned long long t_mark = PROF && a.phase_clk && tid == 0 ? wall_clock64() : 0;
@@ -760,9 +762,9 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
     const uint32_t nl0 = nl_l[v0], nl1 = h1 ? nl_l[v1] : 0u;
     load_row<ASZP>(a.peers + (size_t)(v0 * NB + (nl0 >> 11)) * ASZP, r0);
     if (h1) load_row<ASZP>(a.peers + (size_t)(v1 * NB + (nl1 >> 11)) * ASZP, r1);
-    uint32_t pm0 = taken_slots<ASZP>(r0, nl0 & 31u, (nl0 >> 5) & 63u, a.ASZ, mk_l[v0], org, a.fanout);
+    uint32_t pm0 = taken_slots<ASZP>(r0, nl0 & 31u, (nl0 >> 5) & 63u, a.ASZ, mk_l[v0], org, fan);
     uint32_t pm1 = 0;
-    if (h1) pm1 = taken_slots<ASZP>(r1, nl1 & 31u, (nl1 >> 5) & 63u, a.ASZ, mk_l[v1], org, a.fanout);
+    if (h1) pm1 = taken_slots<ASZP>(r1, nl1 & 31u, (nl1 >> 5) & 63u, a.ASZ, mk_l[v1], org, fan);
     if (nf) {  // failed peers burn their fanout slot (gossip.rs:538-541)
 #pragma unroll
       for (int s = 0; s < ASZP; ++s) {
@@ -1111,25 +1113,28 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
   RWG_MARK(6);
 }
 
-template <int ASZP, bool OFF16, int FP, bool PROF>
+template <int ASZP, bool OFF16, int FP, bool PROF, bool PF>
 static hipError_t launch_rwg_p(Engine& e, const RoundArgs& a, size_t lds) {
-  if (e.rwg_attr_lds != lds || e.rwg_attr_prof != PROF) {
-    hipError_t r = hipFuncSetAttribute((const void*)k_round_wg<ASZP, OFF16, FP, PROF>,
+  if (e.rwg_attr_lds != lds || e.rwg_attr_prof != PROF || e.rwg_attr_pf != PF) {
+    hipError_t r = hipFuncSetAttribute((const void*)k_round_wg<ASZP, OFF16, FP, PROF, PF>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (r != hipSuccess) return r;
     e.rwg_attr_lds = lds;
     e.rwg_attr_prof = PROF;
+    e.rwg_attr_pf = PF;
   }
-  hipLaunchKernelGGL((k_round_wg<ASZP, OFF16, FP, PROF>), dim3(e.S + a.rot_on), dim3(RWG_THREADS), lds, e.st, a);
+  hipLaunchKernelGGL((k_round_wg<ASZP, OFF16, FP, PROF, PF>), dim3(e.S + a.rot_on), dim3(RWG_THREADS), lds, e.st, a);
   return hipSuccess;
 }
 
 template <int ASZP, bool OFF16, int FP>
 static hipError_t launch_rwg_fp(Engine& e, const RoundArgs& a, size_t lds) {
   if constexpr (ASZP == 12 && OFF16 && FP == 6) {  // C2's shape: phase clocks available
-    if (a.phase_clk) return launch_rwg_p<ASZP, OFF16, FP, true>(e, a, lds);
+    if (a.phase_clk && !a.sfan) return launch_rwg_p<ASZP, OFF16, FP, true, false>(e, a, lds);
   }
-  return launch_rwg_p<ASZP, OFF16, FP, false>(e, a, lds);
+  // slots of different fanouts: the kernel that loads its slot's own (the uniform kernel is unchanged)
+  if (a.sfan) return launch_rwg_p<ASZP, OFF16, FP, false, true>(e, a, lds);
+  return launch_rwg_p<ASZP, OFF16, FP, false, false>(e, a, lds);
 }
 
 template <int ASZP, bool OFF16>
@@ -1159,7 +1164,7 @@ hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_c
   a.rot_count = rot_clear ? e.rot_count + e.rot_parity : nullptr;
   a.rot_changed = e.rot_changed;
   a.err = e.err; a.phase_clk = e.phase_clk;
-  a.wave_c_max = (e.prm.flags & GS_FLAG_NARROW_WAVE_PATH) ? 24u : 64u; a.N = e.N; a.S = e.S; a.ASZ = e.ASZ; a.fanout = e.fanout; a.fcap = e.fcap; a.PAIRS = e.PAIRS;
+  a.wave_c_max = (e.prm.flags & GS_FLAG_NARROW_WAVE_PATH) ? 24u : 64u; a.N = e.N; a.S = e.S; a.ASZ = e.ASZ; a.fanout = e.fanout; a.sfan = e.fvar ? e.sfan : nullptr; a.fcap = e.fcap; a.PAIRS = e.PAIRS;
   a.record = record ? 1 : 0;
   const size_t lds = round_wg_lds_bytes(e.N, e.fcap, e.ASZP);
   hipError_t r;

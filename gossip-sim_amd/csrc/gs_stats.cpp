@@ -200,10 +200,17 @@ static int64_t nth_largest(const uint64_t* stakes, uint32_t n, uint32_t rank) {
 int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                        const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                        const double* fractions, gs_sim_result** out) {
+  return gs_run_simulations_fanouts(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, nullptr,
+                                    out);
+}
+
+int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                               const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                               const double* fractions, const uint32_t* fanouts, gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
   gs_params prm{};
-  prm.push_fanout = cfg->push_fanout;
+  prm.push_fanout = fanouts ? *std::max_element(fanouts, fanouts + n_sims) : cfg->push_fanout;
   prm.active_set_size = cfg->active_set_size;
   prm.rotation_probability = cfg->rotation_probability;
   prm.seed = cfg->seed;
@@ -224,6 +231,7 @@ int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_
   if (fractions) frac.assign(fractions, fractions + n_sims);
 #define CK(x) do { r = (x); if (r) { gs_destroy(e); return r; } } while (0)
   CK(gs_set_slots(e, slots.data(), n_sims));
+  if (fanouts) CK(gs_set_slot_fanouts(e, fanouts));
   CK(gs_init_active_sets(e));
   for (uint32_t it = 0; it < cfg->iterations; ++it) {
     if (cfg->test_type == 5 && it == cfg->when_to_fail) CK(gs_fail_nodes(e, frac.data()));

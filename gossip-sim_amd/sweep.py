@@ -13,9 +13,14 @@ every rank. Adding zeros to bit patterns is exact, so the assembled results are
 bit-identical to a one-GPU run. With the "nccl" backend (RCCL over xGMI on ROCm)
 the buffer lives on the rank's GPU; with "gloo" it stays on the host.
 
-Test types whose parameter changes the engine itself (active-set-size,
-push-fanout, rotation-probability) give each value its own engine; `run_sweep`
-takes the values and deals them out the same way.
+Test types whose parameter changes the engine's trajectory (active-set-size,
+rotation-probability) give each value its own engine; `run_sweep` takes the values
+and deals them out the same way. The push fanout does not: only run_gossip's
+.take(fanout) reads it, so the sims of a push-fanout sweep are slots of one engine
+with a fanout per slot (run_simulations(fanouts=...)). The reference raises a sim's
+active-set size to its fanout (gossip_main.rs:809-811), which does change the
+trajectory: `fanout_groups` splits the sweep into the sims that share a size, and
+`run_fanout_sweep` runs each such group as one engine.
 """
 import numpy as np
 
@@ -159,8 +164,73 @@ def run_sharded(stakes, *, n_sims, origin_ranks=None, min_ingress=None, threshol
     return allreduce_results(local, n_sims, group=group, device=comm_device)
 
 
+def fanout_groups(fanouts, asz):
+    """Engine plan of a push-fanout sweep: lists of sim indices, one list per engine. Sim
+    i runs with active-set size max(asz, fanouts[i]) (gossip_main.rs:809-811); sims of equal
+    size form one group, in sim order (groups in order of their first sim)."""
+    groups = {}
+    for i, f in enumerate(fanouts):
+        groups.setdefault(max(int(asz), int(f)), []).append(i)
+    return list(groups.values())
+
+
+def fanout_units(fanouts, asz, world):
+    """The engines of a push-fanout sweep over `world` ranks, as (rank, sim indices) in
+    engine order: the groups of fanout_groups, dealt round-robin when there are at least
+    as many as ranks; with fewer, the largest unit is halved (contiguous sims, the first
+    such unit on ties) until every rank has one or only single sims remain."""
+    units = fanout_groups(fanouts, asz)
+    while len(units) < world:
+        k = max(range(len(units)), key=lambda j: (len(units[j]), -j))
+        if len(units[k]) < 2:
+            break
+        u = units[k]
+        units[k:k + 1] = [u[:(len(u) + 1) // 2], u[(len(u) + 1) // 2:]]
+    return [(j % world, u) for j, u in enumerate(units)]
+
+
+def run_fanout_sweep(stakes, fanouts, make_cfg, *, group=None, device=None, comm_device=None, runner=None):
+    """A push-fanout sweep (test type 3): every group of fanout_groups as ONE engine with a
+    fanout per slot, the engines dealt over the ranks (fanout_units). make_cfg(fanout) ->
+    kwargs of run_simulations for that value, as for run_sweep; its `asz` (default 12) is
+    the size before the reference's raise, and everything but `fanout` / `asz` must agree
+    within a group. Results are bit-identical to run_sweep over the same values."""
+    tdist, rank, world = _dist_info(group)
+    runner = runner or run_simulations
+    cfgs = [dict(make_cfg(f)) for f in fanouts]
+    base = {c.get("asz", 12) for c in cfgs}
+    if len(base) > 1:
+        raise ValueError("run_fanout_sweep: make_cfg must give every value the same asz")
+    asz = base.pop() if base else 12
+    local = {}
+    for r, sims in fanout_units(fanouts, asz, world):
+        if r != rank:
+            continue
+        kw = dict(cfgs[sims[0]])
+        per_sim = ("origin_ranks", "min_ingress", "thresholds", "fractions")  # (one value per sim: joined)
+        skip = ("fanout", "asz", "n_sims") + per_sim
+        for i in sims[1:]:
+            if {k: v for k, v in cfgs[i].items() if k not in skip} != {k: v for k, v in kw.items() if k not in skip}:
+                raise ValueError("run_fanout_sweep: the sims of a group differ in more than the fanout")
+        for k in per_sim:
+            if kw.get(k) is not None:
+                kw[k] = [x for i in sims for x in cfgs[i][k]]
+        kw.pop("n_sims", None)
+        fo = [int(fanouts[i]) for i in sims]
+        kw["fanout"] = max(fo)
+        kw["asz"] = max(asz, fo[0])
+        if device is not None:
+            kw["device"] = device
+        res = runner(stakes, n_sims=len(sims), fanouts=fo, **kw)
+        for j, i in enumerate(sims):
+            local[i] = {(kind, name): (res.f64(j, name) if kind == "f" else res.u64(j, name))
+                        for kind, name in NAMES}
+    return allreduce_results(local, len(fanouts), group=group, device=comm_device)
+
+
 def run_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_device=None, runner=None):
-    """Engine-changing test types (active-set-size, push-fanout, rotation-probability):
+    """Engine-changing test types (active-set-size, rotation-probability; a push-fanout
+    sweep batches instead, run_fanout_sweep):
     one single-sim engine per value, values dealt round-robin over the ranks.
     make_cfg(value) -> kwargs of run_simulations for that value."""
     tdist, rank, world = _dist_info(group)

@@ -19,7 +19,11 @@
  *    one reference Cluster run: its own origin, prune/cache overlay, failed set
  *    and statistics. Sims that share seed/fanout/active-set-size/rotation
  *    probability (an origin-rank, min-ingress, prune-threshold or fail-nodes
- *    sweep, or "all origins") batch into one engine.
+ *    sweep, or "all origins") batch into one engine. The push fanout may also differ per
+ *    slot (gs_set_slot_fanouts): it is read only by run_gossip's .take(fanout)
+ *    (gossip.rs:527-536), never by initialize_gossip, rotation or the weighted shuffle, so
+ *    sims that differ only in fanout share the trajectory too, and a push-fanout sweep
+ *    batches like the others (its sims with the same active-set size, see sweep.py).
  *  - The engine owns all device memory. Inputs are copied at call time; outputs
  *    go to caller buffers with explicit capacities (too small => GS_ERANGE).
  *  - An engine is not re-entrant; use one engine per device per host thread.
@@ -132,6 +136,17 @@ const char* gs_last_error(void);
 const char* gs_kernel_hash(void);
 int gs_device_count(int* n); /* HIP devices visible to this process (0 without a GPU) */
 int gs_set_slots(gs_engine* e, const gs_slot* slots, uint32_t n_slots);
+/* Per-slot Config::gossip_push_fanout: fanout[j] (n_slots values) is slot j's, each in
+ * [1, params.push_fanout], else GS_EINVAL (gs_last_error names the slot) and nothing
+ * changes. params.push_fanout is the engine's capacity: every buffer and kernel variant
+ * stays sized by it, nothing is reallocated. NULL restores the uniform params.push_fanout.
+ * Allowed whenever gs_set_slots is (before or after it; slot state is kept); takes effect at
+ * the next gs_run_gossip / gs_round / gs_part_round / gs_part_xbfs_begin. An engine that never
+ * receives the call, or whose values are all equal, runs the scalar-fanout kernels' path.
+ * On node-range partition ranks the array is replicated state, like the slots: every rank
+ * must be given the same values. gs_get_slot_fanouts reads the values back. */
+int gs_set_slot_fanouts(gs_engine* e, const uint32_t* fanout /*[n_slots]*/);
+int gs_get_slot_fanouts(gs_engine* e, uint32_t* out /*[n_slots]*/);
 int gs_sync(gs_engine* e); /* waits for the stream and reports deferred device-side errors */
 
 /* --- active sets: push_active_set.rs -------------------------------------- */
@@ -311,10 +326,18 @@ typedef struct gs_sim_config {  /* gossip.rs Config (gossip.rs:111-133) */
 
 typedef struct gs_sim_result gs_sim_result;
 /* Runs n_sims simulations that share one active-set trajectory as slots of one
- * engine; sims differ only in origin_rank / min_ingress / threshold / fraction. */
+ * engine; sims differ only in origin_rank / min_ingress / threshold / fraction (and, with
+ * gs_run_simulations_fanouts, push fanout). */
 int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_sims,
                        const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                        const double* fractions, gs_sim_result** out);
+/* The same with a push fanout per sim (a push-fanout sweep at one active-set size as one
+ * engine): fanouts == NULL is exactly gs_run_simulations (every sim takes cfg->push_fanout);
+ * otherwise the engine is created with push_fanout = max(fanouts) and the per-slot values
+ * are set (gs_set_slot_fanouts) before gs_init_active_sets. */
+int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_sims,
+                               const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                               const double* fractions, const uint32_t* fanouts, gs_sim_result** out);
 void gs_result_free(gs_sim_result* r);
 /* Named arrays of a finished sim (same names as the oracle): e.g. "coverage",
  * "rmr", "coverage_stats", "stranded", "hops_hist" ... Returns the element
