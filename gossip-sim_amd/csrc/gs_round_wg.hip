@@ -10,9 +10,9 @@
 //      HBM; per-pair hops/in-degree/egress and the measured-round statistics are
 //      written in the same pass;
 //   C  consume_messages + ReceivedCache::record (gossip.rs:618-653,
-//      received_cache.rs:27-36,83-98): per receiving node, its records sorted by
-//      (hop, id) in registers, looked up in the node's cache entry (HBM,
-//      slot-major rows, coalesced across lanes);
+//      received_cache.rs:27-36,83-98): per receiving node, its records (the two
+//      smallest by (hop, id) picked out, the rest unordered) in registers, looked up
+//      in the node's cache entry (HBM, slot-major rows, coalesced across lanes);
 //   D  send_prunes + ReceivedCache::prune + prune_connections (gossip.rs:657-737,
 //      received_cache.rs:38-63,100-131) for the entries that reached 20 upserts:
 //      (score, stake) order as one 31-bit key ((127 - score) << 24 | stake rank)
@@ -212,14 +212,14 @@ __device__ inline uint32_t off_fetch_inc(uint32_t* offw, uint32_t w, bool pu, ui
   return atomicAdd(pu ? &offw[w] : dummy, pu ? 1u : 0u);
 }
 
-// Bit j set when record j's id (low 16 bits of rk[j]) equals k, for j < NC (records
-// past the in-degree are 0xFFFFFFFF and their bits are never consulted).
 typedef unsigned short rwg_u16x2 __attribute__((ext_vector_type(2)));
 
 // Presence of record ids (u16: N < 2^16 here) in the cache entry, two records per
-// register: x = pair ^ (key | key << 16) has a zero half where the key matches, and a
-// packed u16 min (one v_pk_min_u16) keeps, per half, the smallest x seen -- zero iff
-// that record's id is in the entry. One xor and one min per key per TWO records.
+// register (pk[h] = id of record 2h | id of record 2h + 1 << 16; the halves past the
+// in-degree hold 0xFFFF and their results are never consulted): x = pair ^ (key | key << 16)
+// has a zero half where the key matches, and a packed u16 min (one v_pk_min_u16) keeps, per
+// half, the smallest x seen -- zero iff that record's id is in the entry. One xor and one
+// min per key per TWO records.
 template <int NP2>
 __device__ inline void match_pairs(const uint32_t (&pk)[8], uint32_t k2, uint32_t (&mn)[8]) {
 #pragma unroll
@@ -231,43 +231,61 @@ __device__ inline void match_pairs(const uint32_t (&pk)[8], uint32_t k2, uint32_
 }
 
 // ---- C: register path (1 <= c <= 16) ----
-__device__ inline void consume_lane(const RoundArgs& a, size_t p, const uint16_t* recs, const uint8_t* hops_l,
-                                    uint32_t c, uint32_t& len, uint32_t& up, uint32_t& errf) {
+// ReceivedCache::record (received_cache.rs:83-98) needs the records' order only for its two
+// smallest (hop, id) keys (the timely ones) and, when the 50-key limit cuts the round's
+// insertions short, to decide which records still get in. The entry is a map and the row
+// order of ckey is unspecified, so the records are not sorted: the two smallest
+// keys come from a running min/max, the other absent ids are appended in record order.
+// A round that the limit would cut (or that would pass CACHE_CAP) stores nothing and
+// returns false: the caller hands the node to the wave path, which ranks its records.
+__device__ inline bool consume_lane(const RoundArgs& a, size_t p, const uint16_t* recs, const uint8_t* hops_l,
+                                    uint32_t c, uint32_t& len, uint32_t& up) {
   const size_t PAIRS = a.PAIRS;
   const uint32_t q = (uint32_t)p;
-  uint32_t rk[16];
   const uint32_t wc = active_max<5>(c);
+  // the entry's first eight rows are requested before the records are read from LDS (no
+  // sorted-record array is live beside them), so their round trip overlaps that work
+  const uint32_t wl = active_max<7>(len);
+  uint32_t kc[8];
 #pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    rk[j] = 0xFFFFFFFFu;
-    if ((uint32_t)j < wc) {
-      const uint32_t s = recs[min((uint32_t)j, c - 1)];
-      const uint32_t key = ((uint32_t)hops_l[s] << 16) | s;  // (hop, id): hop = dist[src] + 1 shifts all alike
-      rk[j] = (uint32_t)j < c ? key : 0xFFFFFFFFu;
-    }
-  }
-  // records beyond wc are 0xFFFFFFFF already, so sorting the first 4/8/16 suffices
-  if (wc <= 4) sort_net<4>(rk);
-  else if (wc <= 8) sort_net<8>(rk);
-  else if (wc <= 12) sort_net<16, 16, 12>(rk);
-  else sort_net<16>(rk);
-  // ids of ranks 2h, 2h + 1 in one register (padding ranks carry 0xFFFF, which no key
-  // below equals: ids are < N <= 65,535 and an unused row reads as 0xFFFF)
+  for (int t = 0; t < 8; ++t) kc[t] = (uint32_t)t < wl ? ntl(&(a.ckey + (size_t)t * PAIRS)[q]) : 0u;
+  asm volatile("" ::: "memory");
+  // ids of records 2h, 2h + 1 in one register (padding records carry 0xFFFF, which no key
+  // below equals: ids are < N <= 65,535 and an unused row reads as 0xFFFF); m0 < m1: the two
+  // smallest hop << 20 | id << 4 | record index (hop = dist[src] + 1 shifts all alike; a
+  // source pushes to a node once, so the ids differ and the index never decides)
   uint32_t pk[8], mn[8];
+  uint32_t m0 = 0xFFFFFFFFu, m1 = 0xFFFFFFFFu;
 #pragma unroll
   for (int h = 0; h < 8; ++h) {
-    pk[h] = (rk[2 * h] & 0xFFFFu) | (rk[2 * h + 1] << 16);
+    uint32_t id[2] = {0xFFFFu, 0xFFFFu};
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int j = 2 * h + t;
+      if ((uint32_t)j < wc) {
+        const uint32_t s = recs[min((uint32_t)j, c - 1)];
+        const uint32_t key = (uint32_t)j < c ? ((uint32_t)hops_l[s] << 20) | (s << 4) | (uint32_t)j : 0xFFFFFFFFu;
+        id[t] = (uint32_t)j < c ? s : 0xFFFFu;
+        const uint32_t hi = max(m0, key);
+        m0 = min(m0, key);
+        m1 = min(m1, hi);
+      }
+    }
+    pk[h] = id[0] | (id[1] << 16);
     mn[h] = 0xFFFFFFFFu;
   }
-  const uint32_t id0 = rk[0] & 0xFFFFu, id1 = rk[1] & 0xFFFFu;
+  const uint32_t id0 = (m0 >> 4) & 0xFFFFu, id1 = (m1 >> 4) & 0xFFFFu;
   // look the records up in the entry: rows streamed 8 at a time, loads issued together
   uint32_t w0 = 0, w1 = 0;
   int idx0 = -1, idx1 = -1;
-  const uint32_t wl = active_max<7>(len);
   for (uint32_t i0 = 0; i0 < wl; i0 += 8) {
-    uint32_t kc[8];
+    // the next eight rows are requested before these eight are matched
+    uint32_t kn[8];
+    const bool more = i0 + 8 < wl;
+    if (more) {
 #pragma unroll
-    for (int t = 0; t < 8; ++t) kc[t] = i0 + t < wl ? ntl(&(a.ckey + (size_t)(i0 + t) * PAIRS)[q]) : 0u;
+      for (int t = 0; t < 8; ++t) kn[t] = i0 + 8 + t < wl ? ntl(&(a.ckey + (size_t)(i0 + 8 + t) * PAIRS)[q]) : 0u;
+    }
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -280,33 +298,44 @@ __device__ inline void consume_lane(const RoundArgs& a, size_t p, const uint16_t
       if (k == id0) { idx0 = (int)i; w0 = kc[t]; }
       if (k == id1) { idx1 = (int)i; w1 = kc[t]; }
     }
+    if (more) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) kc[t] = kn[t];
+    }
   }
   uint32_t present = 0;
 #pragma unroll
   for (int j = 0; j < 16; ++j) present |= (uint32_t)(((mn[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) == 0u) << j;
-  idx0 = c > 0 ? idx0 : -1;
   idx1 = c > 1 ? idx1 : -1;
+  // absent records other than the two timely ones; lt: the length after the timely inserts
+  uint32_t newm = ~present & ((1u << c) - 1u) & ~(1u << (m0 & 15u));
+  if (c > 1) newm &= ~(1u << (m1 & 15u));
+  const uint32_t lt = len + (uint32_t)(idx0 < 0) + (uint32_t)(c > 1 && idx1 < 0);
+  if (lt > CACHE_CAP || (lt < CACHE_LIMIT && lt + (uint32_t)__popc(newm) > CACHE_LIMIT)) return false;
+  if (lt >= CACHE_LIMIT) newm = 0;  // full: only timely records are inserted (received_cache.rs:91-97)
   up = up < 255 ? up + 1 : 255;  // rank 0 (received_cache.rs:84-86)
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {  // timely: score += 1, inserted regardless of the 50-key cap
+  for (int j = 0; j < 2; ++j) {  // timely: score += 1, inserted regardless of the 50-key limit
     if ((uint32_t)j >= c) break;
     const int idx = j == 0 ? idx0 : idx1;
     if (idx >= 0) {
       nts(&(a.ckey + (size_t)idx * PAIRS)[q], ck_bump(j == 0 ? w0 : w1));
-    } else if (len < CACHE_CAP) {
-      nts(&(a.ckey + (size_t)len * PAIRS)[q], ck_make(rk[j] & 0xFFFFu, 1u));
-      ++len;
     } else {
-      errf |= ERR_CACHE;
-    }
-  }
-#pragma unroll
-  for (int j = 2; j < 16; ++j) {  // rank order; inserted only while len < 50 (received_cache.rs:91-97)
-    if ((uint32_t)j < c && !((present >> j) & 1u) && len < CACHE_LIMIT) {
-      nts(&(a.ckey + (size_t)len * PAIRS)[q], ck_make(rk[j] & 0xFFFFu, 0u));
+      nts(&(a.ckey + (size_t)len * PAIRS)[q], ck_make(j == 0 ? id0 : id1, 1u));
       ++len;
     }
   }
+  if (__ballot(newm != 0)) {  // (wave-uniform: most rounds find every record of the wave's nodes cached)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {  // all of them fit below the limit: any order gives the same entry
+      if ((uint32_t)j >= wc) break;
+      if ((newm >> j) & 1u) {
+        nts(&(a.ckey + (size_t)len * PAIRS)[q], ck_make((pk[j >> 1] >> (16 * (j & 1))) & 0xFFFFu, 0u));
+        ++len;
+      }
+    }
+  }
+  return true;
 }
 
 // ---- D: register path (len <= 32). Rows are rewritten in prune order with the
@@ -367,7 +396,8 @@ __device__ inline uint32_t prune_lane(const RoundArgs& a, uint32_t* mkw, const u
   return npr;
 }
 
-// ---- C: wave path (16 < c <= 64), all 64 lanes on one node; len/up uniform ----
+// ---- C: wave path (1 <= c <= 64), all 64 lanes on one node; len/up uniform: in-degrees above
+// 16, and the nodes of the register path whose round the 50-key limit cuts short ----
 __device__ inline void consume_wave(const RoundArgs& a, size_t p, const uint16_t* recs, const uint8_t* hops_l,
                                     uint32_t c, uint32_t& len, uint32_t& up, uint32_t* scr, uint32_t& errf) {
   const size_t PAIRS = a.PAIRS;
@@ -979,7 +1009,10 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
       continue;
     }
     uint32_t len = meta & 0xFF, up = (meta >> 8) & 0xFF;
-    if (c) consume_lane(a, p, rec_l + (off_l[v] - c), hops_l, c, len, up, errf);
+    if (c && !consume_lane(a, p, rec_l + (off_l[v] - c), hops_l, c, len, up)) {  // the 50-key limit cuts in
+      hv_l[atomicAdd(&ctrl[C_NHC], 1u)] = (uint16_t)v;
+      continue;
+    }
     if (up >= MIN_NUM_UPSERTS) {
       if (len > (uint32_t)LANE_L) {
         nts(&a.cmeta[p], len | (up << 8));
