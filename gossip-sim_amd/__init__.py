@@ -50,6 +50,10 @@ class Slot(C.Structure):
     _fields_ = [("origin", C.c_uint32), ("min_ingress_nodes", C.c_uint32), ("prune_stake_threshold", C.c_double)]
 
 
+class Traj(C.Structure):  # gs_traj: one active-set trajectory table of a gs_create_traj engine
+    _fields_ = [("active_set_size", C.c_uint32), ("rotation_probability", C.c_double), ("n_slots", C.c_uint32)]
+
+
 class RoundSummary(C.Structure):
     _fields_ = [("visited", C.c_uint32), ("pushes", C.c_uint32), ("prunes", C.c_uint32), ("stranded", C.c_uint32),
                 ("hop_sum", C.c_uint64), ("hop_count", C.c_uint32), ("hop_min", C.c_uint32),
@@ -103,6 +107,18 @@ EXPORTS = {
     "gs_part_stats_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "gs_part_stats_in": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "gs_create": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "gs_create_traj": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                 C.POINTER(C.c_void_p)]),
+    "gs_engine_traj": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "gs_traj_supported": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
+    "gs_set_active_set_entry_traj": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                               C.c_uint32]),
+    "gs_get_active_set_entry_traj": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                               C.c_uint32, C.POINTER(C.c_uint32)]),
+    "gs_read_active_sets_traj": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "gs_run_simulations_traj": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_void_p)]),
     "gs_destroy": (None, [C.c_void_p]),
     "gs_set_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "gs_set_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -230,14 +246,31 @@ def ids_from_pubkeys(pubkeys):
     return ids
 
 
+def traj_supported(n, fanout, max_asz):
+    """(supported, fused): can a network of n nodes run as a trajectory-table engine with this
+    push-fanout capacity and largest active-set size, and would its round be the one-kernel
+    one. Host arithmetic of the workgroup engine's LDS rule; needs no device."""
+    fused = C.c_int()
+    ok = lib().gs_traj_supported(int(n), int(fanout), int(max_asz), C.byref(fused))
+    return bool(ok), bool(fused.value)
+
+
 class Engine:
-    """One engine = one device + one shared active-set trajectory + n_slots sims."""
+    """One engine = one device + n_slots sims on one shared active-set trajectory, or, with
+    trajectories=[(active_set_size, rotation_probability, n_slots), ...], on several tables:
+    table t serves the next n_slots slots (their counts sum to the engine's), the capacity is
+    the largest size, and `active_set_size` / `rotation_probability` are unused."""
 
     def __init__(self, stakes, n_slots, *, fanout=6, active_set_size=12, rotation_probability=0.013333, seed=0,
                  device=0, bfs_mode=GS_BFS_AUTO, inbound_capacity=0, profile=False, split_round=False,
                  narrow_wave_path=False, binned_all_levels=False, wide_records=False, no_small_levels=False,
-                 mispredict_levels=False, frontier_exchange=False, part=None):
+                 mispredict_levels=False, frontier_exchange=False, part=None, trajectories=None):
         L = lib()
+        if trajectories is not None:
+            if part is not None:
+                raise ValueError("Engine: partition ranks take no trajectory tables")
+            trajectories = [(int(a), float(q), int(k)) for a, q, k in trajectories]
+            active_set_size = max([a for a, _, _ in trajectories], default=active_set_size)
         self.stakes = np.ascontiguousarray(stakes, dtype=np.uint64)
         self.n = len(self.stakes)
         self.n_slots = n_slots
@@ -250,7 +283,11 @@ class Engine:
                    (GS_FLAG_MISPREDICT_LEVELS if mispredict_levels else 0) |
                    (GS_FLAG_FRONTIER_EXCHANGE if frontier_exchange else 0))
         h = C.c_void_p()
-        if part is None:
+        if trajectories is not None:
+            arr = (Traj * max(1, len(trajectories)))(*[Traj(a, q, k) for a, q, k in trajectories])
+            _check(L.gs_create_traj(C.byref(p), _ptr(self.stakes), self.n, n_slots, C.cast(arr, C.c_void_p),
+                                    len(trajectories), C.byref(h)))
+        elif part is None:
             _check(L.gs_create(C.byref(p), _ptr(self.stakes), self.n, n_slots, C.byref(h)))
         else:  # (rank, nranks): one rank of a node-range partition (gossip_sim_amd.partition)
             _check(L.gs_create_part(C.byref(p), _ptr(self.stakes), self.n, n_slots, part[0], part[1], C.byref(h)))
@@ -308,14 +345,27 @@ class Engine:
     def init_active_sets(self):
         _check(lib().gs_init_active_sets(self.h))
 
-    def set_entry(self, node, bucket, peers):
-        a = np.ascontiguousarray(peers, dtype=np.uint32)
-        _check(lib().gs_set_active_set_entry(self.h, node, bucket, _ptr(a), len(a)))
+    def trajectories(self):
+        """The engine's tables: [(active_set_size, rotation_probability, n_slots), ...]."""
+        n = C.c_uint32()
+        arr = (Traj * 256)()
+        _check(lib().gs_engine_traj(self.h, C.cast(arr, C.c_void_p), 256, C.byref(n)))
+        return [(arr[t].active_set_size, arr[t].rotation_probability, arr[t].n_slots) for t in range(n.value)]
 
-    def get_entry(self, node, bucket):
+    def set_entry(self, node, bucket, peers, table=None):
+        a = np.ascontiguousarray(peers, dtype=np.uint32)
+        if table is None:
+            _check(lib().gs_set_active_set_entry(self.h, node, bucket, _ptr(a), len(a)))
+        else:
+            _check(lib().gs_set_active_set_entry_traj(self.h, table, node, bucket, _ptr(a), len(a)))
+
+    def get_entry(self, node, bucket, table=None):
         out = np.zeros(64, dtype=np.uint32)
         ln = C.c_uint32()
-        _check(lib().gs_get_active_set_entry(self.h, node, bucket, _ptr(out), 64, C.byref(ln)))
+        if table is None:
+            _check(lib().gs_get_active_set_entry(self.h, node, bucket, _ptr(out), 64, C.byref(ln)))
+        else:
+            _check(lib().gs_get_active_set_entry_traj(self.h, table, node, bucket, _ptr(out), 64, C.byref(ln)))
         return [int(x) for x in out[:ln.value]]
 
     def fail_nodes(self, fractions):
@@ -390,12 +440,19 @@ class Engine:
         _check(lib().gs_read_pruned(self.h, slot, node, C.byref(m)))
         return m.value
 
-    def active_sets(self):
-        """(peers[n, 25, asz] FIFO order, lens[n, 25])."""
+    def active_sets(self, table=None):
+        """(peers[n, 25, asz] FIFO order, lens[n, 25]); table: one of a trajectory-table engine's
+        (asz is then that table's own size)."""
         asz = self.active_set_size
+        if table is not None:
+            tr = self.trajectories()
+            asz = tr[table][0] if 0 <= table < len(tr) else asz  # (out of range: refused by the call below)
         peers = np.zeros(self.n * 25 * asz, dtype=np.uint32)
         lens = np.zeros(self.n * 25, dtype=np.uint8)
-        _check(lib().gs_read_active_sets(self.h, _ptr(peers), _ptr(lens)))
+        if table is None:
+            _check(lib().gs_read_active_sets(self.h, _ptr(peers), _ptr(lens)))
+        else:
+            _check(lib().gs_read_active_sets_traj(self.h, table, _ptr(peers), _ptr(lens)))
         return peers.reshape(self.n, 25, asz), lens.reshape(self.n, 25)
 
     def caches(self, slot):
@@ -518,9 +575,11 @@ class SimResult:
 def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, thresholds=None, fractions=None,
                     fanout=6, asz=12, iterations=1, warm_up=200, p=0.013333, thr=0.15, min_ingress_nodes=2,
                     fraction_to_fail=0.1, when_to_fail=0, nb_stranded=10, nb_message=5, nb_hops=15, test_type=0,
-                    seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None):
-    """gossip_main.rs run_simulation for n_sims sims sharing one trajectory (one engine).
-    fanouts: a push fanout per sim (the engine's capacity is their maximum; `fanout` is unused then)."""
+                    seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None, aszs=None, rot_probs=None):
+    """gossip_main.rs run_simulation for n_sims sims as slots of one engine.
+    fanouts: a push fanout per sim (the engine's capacity is their maximum; `fanout` is unused then).
+    aszs / rot_probs: an active-set size / rotation probability per sim (default `asz` / `p`); sims
+    with equal pairs share a trajectory table of one engine, and results stay in sim order."""
     st = np.ascontiguousarray(stakes, dtype=np.uint64)
     cfg = SimConfig(fanout, asz, iterations, warm_up, min_ingress_nodes, when_to_fail, p, thr, fraction_to_fail,
                     nb_stranded, nb_message, nb_hops, test_type, seed, device, bfs_mode)
@@ -533,9 +592,20 @@ def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, th
     fo = arr(fanouts, np.uint32)
     if fo is not None and fo.shape != (n_sims,):
         raise ValueError(f"run_simulations: fanouts needs exactly n_sims = {n_sims} values")
+    az, rp = arr(aszs, np.uint32), arr(rot_probs, np.float64)
+    for name, x in (("aszs", az), ("rot_probs", rp)):
+        if x is not None and x.shape != (n_sims,):
+            raise ValueError(f"run_simulations: {name} needs exactly n_sims = {n_sims} values")
     h = C.c_void_p()
-    _check(lib().gs_run_simulations_fanouts(C.byref(cfg), _ptr(st), len(st), n_sims,
-                                            None if r is None else _ptr(r), None if mi is None else _ptr(mi),
-                                            None if th is None else _ptr(th), None if fr is None else _ptr(fr),
-                                            None if fo is None else _ptr(fo), C.byref(h)))
+    if az is None and rp is None:
+        _check(lib().gs_run_simulations_fanouts(C.byref(cfg), _ptr(st), len(st), n_sims,
+                                                None if r is None else _ptr(r), None if mi is None else _ptr(mi),
+                                                None if th is None else _ptr(th), None if fr is None else _ptr(fr),
+                                                None if fo is None else _ptr(fo), C.byref(h)))
+    else:
+        _check(lib().gs_run_simulations_traj(C.byref(cfg), _ptr(st), len(st), n_sims,
+                                             None if r is None else _ptr(r), None if mi is None else _ptr(mi),
+                                             None if th is None else _ptr(th), None if fr is None else _ptr(fr),
+                                             None if fo is None else _ptr(fo), None if az is None else _ptr(az),
+                                             None if rp is None else _ptr(rp), C.byref(h)))
     return SimResult(h, n_sims)

@@ -75,6 +75,7 @@ struct Cli {
   std::string save_results, replay_results, engine_plan;
   std::string influx_file;  // offline Influx line protocol (gs_influx.cpp)
   uint64_t influx_time_base = 0;
+  bool batch_sweeps = false;  // an active-set-size / rotate-probability / push-fanout sweep as one engine per device
 };
 
 void usage() {
@@ -96,6 +97,9 @@ void usage() {
       "  --seed S [0x5EED0003] --gpus K [1] --bfs-mode 0..5 [0 = auto; 1 workgroup, 2 level, 3 binned, 4 multi, 5 hybrid]\n"
       "  --save-results PATH  --replay-results PATH (print the report of a saved run, no GPU)\n"
       "  --engine-plan PATH   write one line per engine: device, simulations, active-set size, fanouts\n"
+      "  --batch-sweeps       run an active-set-size, rotate-probability or push-fanout sweep as ONE engine per\n"
+      "                       device (an active-set table per value) instead of one engine per value; a plan\n"
+      "                       line then lists active-set-size, fanouts and rotation-probability per simulation\n"
       "  --influx-file PATH   write the Influx series (influx_db.rs) as line protocol to PATH\n"
       "  --influx-time-base NS  reproducible Influx timestamps NS + 1000 k (default: wall clock)\n"
       "gossip-sim write-accounts --account-file PATH --synthetic N [--num-nodes K] [--zero-stakes] [-f]");
@@ -169,6 +173,7 @@ Cli parse(int argc, char** argv) {
     else if (a == "--engine-plan") c.engine_plan = need(i);
     else if (a == "--influx-file") c.influx_file = need(i);
     else if (a == "--influx-time-base") u64(i, c.influx_time_base);
+    else if (a == "--batch-sweeps") c.batch_sweeps = true;
     else die(2, "unexpected argument '" + a + "' (see --help)");
   }
   return c;
@@ -214,6 +219,9 @@ struct Job {
   std::vector<double> thr, frac;
   std::vector<uint32_t> fanouts;  // per simulation
   bool slot_fanouts = false;      // a push-fanout sweep: the engine takes `fanouts` per slot
+  bool traj = false;              // --batch-sweeps: an active-set table per (size, probability) of `aszs` / `probs`
+  std::vector<uint32_t> aszs;     // per simulation
+  std::vector<double> probs;
 };
 
 void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsrep::SimArrays>& out,
@@ -221,9 +229,13 @@ void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsre
   gs_sim_config cfg = j.cfg;
   cfg.device = j.device;
   gs_sim_result* r = nullptr;
-  const int rc = gs_run_simulations_fanouts(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
-                                            j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(),
-                                            j.slot_fanouts ? j.fanouts.data() : nullptr, &r);
+  const int rc =
+      j.traj ? gs_run_simulations_traj(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+                                       j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(), j.fanouts.data(),
+                                       j.aszs.data(), j.probs.data(), &r)
+             : gs_run_simulations_fanouts(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+                                          j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(),
+                                          j.slot_fanouts ? j.fanouts.data() : nullptr, &r);
   if (rc) {
     err = std::string("gs_run_simulations: ") + gs_last_error();
     return;
@@ -390,9 +402,25 @@ int main(int argc, char** argv) {
       return cfg;
     };
     const bool per_value_engine = test_type == gsrep::ACTIVE_SET_SIZE || test_type == gsrep::ROTATE_PROBABILITY;
-    // batches: sims that share a trajectory, in simulation order
+    // --batch-sweeps: the sweeps whose value changes the trajectory (and a push-fanout sweep's
+    // sims of raised size) as tables of one engine, when the network fits the workgroup engine
+    bool traj = c.batch_sweeps && (per_value_engine || test_type == gsrep::PUSH_FANOUT);
+    if (traj) {
+      uint64_t fmax = 1, amax = 1;
+      for (const auto& q : params) { fmax = std::max(fmax, q.gossip_push_fanout); amax = std::max(amax, q.gossip_active_set_size); }
+      if (amax > GS_MAX_ACTIVE_SET_SIZE ||
+          !gs_traj_supported((uint32_t)stakes.size(), (uint32_t)std::min<uint64_t>(fmax, 0xFFFFFFFFu), (uint32_t)amax, nullptr)) {
+        gsrep::log_info(stderr, TMAIN, "--batch-sweeps: " + std::to_string(stakes.size()) + " nodes at active-set size " +
+                                           std::to_string(amax) + " do not fit the workgroup engine; planning one engine per value");
+        traj = false;
+      }
+    }
+    // batches: sims that share a trajectory (or, batched, an engine), in simulation order
     std::vector<std::vector<size_t>> batches;
-    if (per_value_engine) {
+    if (traj) {
+      batches.emplace_back();
+      for (size_t i = 0; i < num_sims; ++i) batches[0].push_back(i);
+    } else if (per_value_engine) {
       for (size_t i = 0; i < num_sims; ++i) batches.push_back({i});
     } else if (test_type == gsrep::PUSH_FANOUT) {  // the sims of one (raised) active-set size
       for (size_t i = 0; i < num_sims; ++i) {
@@ -420,14 +448,17 @@ int main(int argc, char** argv) {
       j.device = (int)(gi % c.gpus);
       j.sims = groups[gi];
       j.slot_fanouts = test_type == gsrep::PUSH_FANOUT;
+      j.traj = traj;
       for (size_t i : groups[gi]) {
+        j.aszs.push_back((uint32_t)params[i].gossip_active_set_size);
+        j.probs.push_back(std::min(params[i].probability_of_rotation, 1.0));
         j.ranks.push_back((uint32_t)params[i].origin_rank);
         j.mi.push_back((uint32_t)params[i].min_ingress_nodes);
         j.thr.push_back(params[i].prune_stake_threshold);
         j.frac.push_back(params[i].fraction_to_fail);
         j.fanouts.push_back((uint32_t)params[i].gossip_push_fanout);
       }
-      if (j.slot_fanouts) j.cfg.push_fanout = *std::max_element(j.fanouts.begin(), j.fanouts.end());
+      if (j.slot_fanouts || j.traj) j.cfg.push_fanout = *std::max_element(j.fanouts.begin(), j.fanouts.end());
       jobs.push_back(std::move(j));
     }
   }
@@ -437,8 +468,18 @@ int main(int argc, char** argv) {
     for (const Job& j : jobs) {
       std::fprintf(f, "device %d sims ", j.device);
       for (size_t k = 0; k < j.sims.size(); ++k) std::fprintf(f, "%s%zu", k ? "," : "", j.sims[k]);
-      std::fprintf(f, " active-set-size %u fanouts ", j.cfg.active_set_size);
+      if (j.traj) {  // per-simulation lists
+        std::fprintf(f, " active-set-size ");
+        for (size_t k = 0; k < j.aszs.size(); ++k) std::fprintf(f, "%s%u", k ? "," : "", j.aszs[k]);
+        std::fprintf(f, " fanouts ");
+      } else {
+        std::fprintf(f, " active-set-size %u fanouts ", j.cfg.active_set_size);
+      }
       for (size_t k = 0; k < j.fanouts.size(); ++k) std::fprintf(f, "%s%u", k ? "," : "", j.fanouts[k]);
+      if (j.traj) {
+        std::fprintf(f, " rotation-probability ");
+        for (size_t k = 0; k < j.probs.size(); ++k) std::fprintf(f, "%s%.17g", k ? "," : "", j.probs[k]);
+      }
       std::fprintf(f, "\n");
     }
     std::fclose(f);

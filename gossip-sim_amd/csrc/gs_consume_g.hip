@@ -62,6 +62,10 @@ struct CgArgs {
   size_t PAIRS;
   int record;
   int zero_sp;  // k_cg_consume zeroes slot_prunes (block 0) for the k_cg_prune that follows
+  // several trajectory tables (else stab is null): slot o's entries are table stab[o]'s
+  const uint32_t* stab;
+  const TrajDev* ttab;
+  size_t t_rows, t_ents;
 };
 
 // ---- consume, register path (1 <= c <= 16) ----
@@ -119,7 +123,14 @@ template <int ASZP>
 __device__ inline void apply_prune(const CgArgs& a, uint32_t o, uint32_t ob, uint32_t u, uint32_t v) {
   const uint32_t bu = a.bucket[u], k = min(bu, ob);
   uint32_t row[ASZP], hv;
-  if (a.own && k == bu) {  // the own-bucket row (64 B, cache-resident) instead of the full table's
+  uint32_t asz = a.ASZ;
+  if (a.stab) {  // (workgroup engines only: no own rows)
+    const uint32_t t = a.stab[o];
+    const uint32_t ent = u * NB + k;
+    asz = a.ttab[t].asz;
+    hv = (a.hl + t * a.t_ents)[ent];
+    load_row<ASZP>(a.peers + t * a.t_rows + (size_t)ent * ASZP, row);
+  } else if (a.own && k == bu) {  // the own-bucket row (64 B, cache-resident) instead of the full table's
     const uint32_t* orow = a.own + (size_t)u * a.ORW;
     load_row<ASZP>(orow, row);
     hv = orow[ASZP] & 0xFFFFu;
@@ -132,8 +143,8 @@ __device__ inline void apply_prune(const CgArgs& a, uint32_t o, uint32_t ob, uin
   uint32_t hit = 0;
 #pragma unroll
   for (int s = 0; s < ASZP; ++s) {
-    const uint32_t pos = (uint32_t)s >= head ? (uint32_t)s - head : (uint32_t)s + a.ASZ - head;
-    hit |= (uint32_t)((uint32_t)s < a.ASZ && pos < L && row[s] == v) << s;
+    const uint32_t pos = (uint32_t)s >= head ? (uint32_t)s - head : (uint32_t)s + asz - head;
+    hit |= (uint32_t)((uint32_t)s < asz && pos < L && row[s] == v) << s;
   }
   if (hit) atomicOr(&a.mask[o * a.mso + u * a.msu], hit);
 }
@@ -486,6 +497,7 @@ hipError_t launch_consume_prune_g(Engine& e, bool record, bool consume, bool zer
   a.N = e.N; a.S = e.S; a.ASZ = e.ASZ; a.capin = e.capin; a.PAIRS = e.PAIRS; a.record = record ? 1 : 0;
   a.mso = e.mso;
   a.msu = e.msu;
+  a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents;
   const bool narrow = (e.prm.flags & GS_FLAG_NARROW_WAVE_PATH) != 0;
   a.zero_sp = consume && zero_slot_prunes ? 1 : 0;
   a.lane_c = narrow ? 4u : 16u;

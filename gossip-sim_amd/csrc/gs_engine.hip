@@ -220,8 +220,10 @@ static size_t part_record_cap(size_t N, size_t S, uint32_t K) {
 
 // K == 0: an engine over all nodes; K >= 1: rank `rank` of a node-range partition over K
 // ranks (K == 1: one rank owning every node, the exchange calls still available).
+// traj != null (gs_create_traj, n_traj >= 2 here): the engine's trajectory tables; prm's
+// active_set_size is then the capacity and its rotation probability is unused.
 static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots, uint32_t rank,
-                         uint32_t K, gs_engine** out) {
+                         uint32_t K, gs_engine** out, const gs_traj* traj = nullptr, uint32_t n_traj = 0) {
   const bool part = K >= 1;
   if (!part) K = 1;
   if (!prm || !stakes || !out) return fail(GS_EINVAL, "null argument");
@@ -254,6 +256,24 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   e->fanout = prm->push_fanout;
   e->fcap = std::min(e->fanout, e->ASZ);
   e->capin = prm->inbound_capacity ? prm->inbound_capacity : 64;
+  e->T = traj ? n_traj : 1;
+  e->t_rows = (size_t)n * NB * e->ASZP;
+  e->t_ents = (size_t)n * NB;
+  e->h_stab.assign(n_slots, 0);
+  if (traj) {
+    uint32_t s0 = 0;
+    for (uint32_t t = 0; t < n_traj; ++t) {
+      TrajTab tt;
+      tt.asz = traj[t].active_set_size; tt.p = traj[t].rotation_probability; tt.s0 = s0; tt.ns = traj[t].n_slots;
+      for (uint32_t o = 0; o < tt.ns; ++o) e->h_stab[s0 + o] = t;
+      s0 += tt.ns;
+      e->traj.push_back(tt);
+    }
+  } else {
+    TrajTab tt;
+    tt.asz = e->ASZ; tt.p = prm->rotation_probability; tt.s0 = 0; tt.ns = n_slots;
+    e->traj.push_back(tt);
+  }
   if (hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking) != hipSuccess) {
     destroy_engine(e);
     return fail(GS_EHIP, "hipStreamCreate");
@@ -297,6 +317,14 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
     e->NP = hi - lo;
     e->vlo = lo;
     e->PAIRS = (size_t)e->NP * n_slots;
+  }
+  if (traj) {  // several tables: the workgroup engine only (its slots already run concurrently)
+    if (mode != GS_BFS_AUTO && mode != GS_BFS_WORKGROUP) {
+      destroy_engine(e);
+      return fail(GS_EINVAL, "gs_create_traj: trajectory tables need bfs_mode GS_BFS_WORKGROUP (or AUTO); the other "
+                             "BFS strategies hold one active-set table");
+    }
+    mode = GS_BFS_WORKGROUP;
   }
   // AUTO, measured: MULTI 2.6 vs BINNED 3.6 ms per C4 round (13 slots); at 10M nodes MULTI wins
   // from 2 slots (4.86 vs 5.26 ms); round 5, with expand grids sized from the level profile, at
@@ -372,8 +400,20 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   ALLOC(e->bucket, N, 0);
   ALLOC(e->P, (size_t)NB * (N + 1), 0);
   ALLOC(e->IX, (size_t)NB * ix_count(n), 0);
-  ALLOC(e->peers, N * NB * e->ASZP, 0);
-  ALLOC(e->hl, N * NB, 0);
+  ALLOC(e->peers, e->T * e->t_rows, 0);
+  ALLOC(e->hl, e->T * e->t_ents, 0);
+  if (e->T > 1) {
+    std::vector<TrajDev> td(e->T);
+    for (uint32_t t = 0; t < e->T; ++t) td[t] = TrajDev{e->traj[t].asz, e->traj[t].s0, e->traj[t].p};
+    ALLOC(e->stab, S, 0);
+    ALLOC(e->ttab, e->T, 0);
+    if (hipMemcpyAsync(e->stab, e->h_stab.data(), S * 4, hipMemcpyHostToDevice, e->st) != hipSuccess ||
+        hipMemcpyAsync(e->ttab, td.data(), e->T * sizeof(TrajDev), hipMemcpyHostToDevice, e->st) != hipSuccess ||
+        hipStreamSynchronize(e->st) != hipSuccess) {
+      destroy_engine(e);
+      return fail(GS_EHIP, "trajectory table upload");
+    }
+  }
   ALLOC(e->frank, N, 0);
   ALLOC(e->srank, N, 0);
   ALLOC(e->by_srank, N, 0);
@@ -482,9 +522,9 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   }
   e->h_nfail_any.assign(S, 0);
   ALLOC(e->lvl, 512, 0);  // [256] level sizes; binned BFS: [256 + d] = 1 iff level d was binned this round
-  ALLOC(e->rot_list, N, 0);
-  ALLOC(e->rot_count, 2, 0);
-  ALLOC(e->rot_changed, N * NB, 0);
+  ALLOC(e->rot_list, e->T * N, 0);
+  ALLOC(e->rot_count, 2 * (size_t)e->T, 0);
+  ALLOC(e->rot_changed, e->T * e->t_ents, 0);
   ALLOC(e->rs_u32, S * 4, 0);
   ALLOC(e->rs_ssum, S, 0);
   ALLOC(e->rs_hist, S * 256, 0);
@@ -571,6 +611,67 @@ int gs_create_part(const gs_params* prm, const uint64_t* stakes, uint32_t n, uin
                    uint32_t nranks, gs_engine** out) {
   if (nranks < 1 || rank >= nranks) return fail(GS_EINVAL, "rank must be < nranks");
   return create_engine(prm, stakes, n, n_slots, rank, nranks, out);
+}
+
+// Host arithmetic of the workgroup engine's LDS rule (no device): the step-wise BFS state and,
+// for *fused, the one-kernel round's layout at the capacity's push masks and record area.
+int gs_traj_supported(uint32_t n_nodes, uint32_t push_fanout, uint32_t max_active_set_size, int* fused) {
+  if (fused) *fused = 0;
+  if (n_nodes < 2 || push_fanout < 1 || max_active_set_size < 1 || max_active_set_size > GS_MAX_ACTIVE_SET_SIZE)
+    return 0;
+  if (n_nodes > 65535 || bfs_wg_lds_bytes(n_nodes) > 160 * 1024) return 0;
+  const uint32_t aszp = (max_active_set_size + 3) & ~3u;
+  if (fused) *fused = round_wg_lds_bytes(n_nodes, std::min(push_fanout, max_active_set_size), aszp) <= 160 * 1024;
+  return 1;
+}
+
+int gs_create_traj(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots, const gs_traj* traj,
+                   uint32_t n_traj, gs_engine** out) {
+  if (!prm || !stakes || !out || !traj) return fail(GS_EINVAL, "null argument");
+  *out = nullptr;
+  if (n_traj == 0) return fail(GS_EINVAL, "gs_create_traj: n_traj must be >= 1");
+  if (prm->active_set_size < 1 || prm->active_set_size > GS_MAX_ACTIVE_SET_SIZE)
+    return fail(GS_EINVAL, "active_set_size must be in [1, 32]");
+  uint64_t sum = 0;
+  for (uint32_t t = 0; t < n_traj; ++t) {
+    const std::string w = "gs_create_traj: table " + std::to_string(t);
+    if (traj[t].n_slots == 0) return fail(GS_EINVAL, w + " serves no slot");
+    if (traj[t].active_set_size < 1 || traj[t].active_set_size > prm->active_set_size)
+      return fail(GS_EINVAL, w + ": active_set_size must be in [1, params.active_set_size = " +
+                                 std::to_string(prm->active_set_size) + "]");
+    if (!(traj[t].rotation_probability >= 0.0 && traj[t].rotation_probability <= 1.0))
+      return fail(GS_EINVAL, w + ": rotation_probability must be in [0, 1]");
+    sum += traj[t].n_slots;
+  }
+  if (sum != n_slots) return fail(GS_EINVAL, "gs_create_traj: the tables' n_slots must sum to n_slots");
+  gs_params p = *prm;
+  if (p.bfs_mode != GS_BFS_AUTO && p.bfs_mode != GS_BFS_WORKGROUP)
+    return fail(GS_EINVAL, "gs_create_traj: trajectory tables need bfs_mode GS_BFS_WORKGROUP (or AUTO); the other "
+                           "BFS strategies hold one active-set table");
+  p.bfs_mode = GS_BFS_WORKGROUP;
+  if (!gs_traj_supported(n, p.push_fanout ? p.push_fanout : 1, p.active_set_size, nullptr) && n >= 2 && n <= GS_MAX_NODES)
+    return fail(GS_EINVAL, "gs_create_traj: the network does not fit the workgroup engine's LDS (gs_traj_supported)");
+  if (n_traj == 1) {  // one table: exactly the engine gs_create makes with that size and probability
+    p.active_set_size = traj[0].active_set_size;
+    p.rotation_probability = traj[0].rotation_probability;
+    return create_engine(&p, stakes, n, n_slots, 0, 0, out);
+  }
+  p.rotation_probability = 0.0;  // (unused: every table carries its own)
+  return create_engine(&p, stakes, n, n_slots, 0, 0, out, traj, n_traj);
+}
+
+int gs_engine_traj(gs_engine* eh, gs_traj* out, uint32_t cap, uint32_t* n_traj) {
+  Engine* e = reinterpret_cast<Engine*>(eh);
+  if (!e || !n_traj) return fail(GS_EINVAL, "null argument");
+  *n_traj = e->T;
+  if (e->T > cap) return fail(GS_ERANGE, "trajectory buffer too small");
+  if (!out) return fail(GS_EINVAL, "null argument");
+  for (uint32_t t = 0; t < e->T; ++t) {
+    out[t].active_set_size = e->traj[t].asz;
+    out[t].rotation_probability = e->traj[t].p;
+    out[t].n_slots = e->traj[t].ns;
+  }
+  return GS_OK;
 }
 
 void gs_destroy(gs_engine* eh) { destroy_engine(reinterpret_cast<Engine*>(eh)); }
@@ -709,11 +810,30 @@ int gs_init_active_sets(gs_engine* eh) {
   return GS_OK;
 }
 
+// The un-suffixed entry calls name no table: refused once the engine holds several.
+static int one_table(Engine* e, const char* call) {
+  if (e->T > 1)
+    return fail(GS_EINVAL, std::string(call) + ": the engine holds " + std::to_string(e->T) +
+                               " trajectory tables; name one with " + call + "_traj");
+  return GS_OK;
+}
+static int table_check(Engine* e, uint32_t t) {
+  return t < e->T ? GS_OK : fail(GS_EINVAL, "trajectory table out of range");
+}
+
 int gs_set_active_set_entry(gs_engine* eh, uint32_t node, uint32_t bucket, const uint32_t* peers, uint32_t len) {
   ENGINE(eh);
+  if (int s_ = one_table(e, "gs_set_active_set_entry")) return s_;
+  return gs_set_active_set_entry_traj(eh, 0, node, bucket, peers, len);
+}
+
+int gs_set_active_set_entry_traj(gs_engine* eh, uint32_t t, uint32_t node, uint32_t bucket, const uint32_t* peers,
+                                 uint32_t len) {
+  ENGINE(eh);
+  if (int s_ = table_check(e, t)) return s_;
   if (int s_ = flush_rot_clear(e)) return s_;
   if (node >= e->N || bucket >= (uint32_t)NB) return fail(GS_EINVAL, "node/bucket out of range");
-  if (len > e->ASZ) return fail(GS_ERANGE, "entry longer than active_set_size");
+  if (len > e->traj[t].asz) return fail(GS_ERANGE, "entry longer than active_set_size");
   std::vector<uint32_t> row(e->ASZP, 0);
   for (uint32_t i = 0; i < len; ++i) {
     if (peers[i] >= e->N || peers[i] == node) return fail(GS_EINVAL, "bad peer id");
@@ -723,11 +843,11 @@ int gs_set_active_set_entry(gs_engine* eh, uint32_t node, uint32_t bucket, const
   }
   const size_t ent = (size_t)node * NB + bucket;
   uint16_t hv = (uint16_t)(len << 8);
-  HIPC(hipMemcpyAsync(e->peers + ent * e->ASZP, row.data(), e->ASZP * 4, hipMemcpyHostToDevice, e->st));
-  HIPC(hipMemcpyAsync(e->hl + ent, &hv, 2, hipMemcpyHostToDevice, e->st));
+  HIPC(hipMemcpyAsync(e->peers + t * e->t_rows + ent * e->ASZP, row.data(), e->ASZP * 4, hipMemcpyHostToDevice, e->st));
+  HIPC(hipMemcpyAsync(e->hl + t * e->t_ents + ent, &hv, 2, hipMemcpyHostToDevice, e->st));
   e->rows2_stale = true;
   HIPC(launch_own_rows(*e, nullptr, nullptr));
-  HIPC(launch_clear_slot_masks(*e, node, bucket, 0xFFFFFFFFu));
+  HIPC(launch_clear_slot_masks(*e, t, node, bucket, 0xFFFFFFFFu));
   HIPC(hipStreamSynchronize(e->st));
   return GS_OK;
 }
@@ -735,17 +855,25 @@ int gs_set_active_set_entry(gs_engine* eh, uint32_t node, uint32_t bucket, const
 int gs_get_active_set_entry(gs_engine* eh, uint32_t node, uint32_t bucket, uint32_t* peers, uint32_t cap,
                             uint32_t* len) {
   ENGINE(eh);
+  if (int s_ = one_table(e, "gs_get_active_set_entry")) return s_;
+  return gs_get_active_set_entry_traj(eh, 0, node, bucket, peers, cap, len);
+}
+
+int gs_get_active_set_entry_traj(gs_engine* eh, uint32_t t, uint32_t node, uint32_t bucket, uint32_t* peers,
+                                 uint32_t cap, uint32_t* len) {
+  ENGINE(eh);
+  if (int s_ = table_check(e, t)) return s_;
   if (node >= e->N || bucket >= (uint32_t)NB) return fail(GS_EINVAL, "node/bucket out of range");
   const size_t ent = (size_t)node * NB + bucket;
   std::vector<uint32_t> row(e->ASZP);
   uint16_t hv = 0;
-  HIPC(hipMemcpyAsync(row.data(), e->peers + ent * e->ASZP, e->ASZP * 4, hipMemcpyDeviceToHost, e->st));
-  HIPC(hipMemcpyAsync(&hv, e->hl + ent, 2, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipMemcpyAsync(row.data(), e->peers + t * e->t_rows + ent * e->ASZP, e->ASZP * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipMemcpyAsync(&hv, e->hl + t * e->t_ents + ent, 2, hipMemcpyDeviceToHost, e->st));
   HIPC(hipStreamSynchronize(e->st));
   const uint32_t head = hv & 0xFF, L = hv >> 8;
   *len = L;
   if (L > cap) return fail(GS_ERANGE, "peers buffer too small");
-  for (uint32_t j = 0; j < L; ++j) peers[j] = row[(head + j) % e->ASZ];
+  for (uint32_t j = 0; j < L; ++j) peers[j] = row[(head + j) % e->traj[t].asz];
   return GS_OK;
 }
 
@@ -907,17 +1035,17 @@ int gs_record_round(gs_engine* eh) {
 // (a partial set left peers2 set and a later round wrote through a null hl2).
 static int ensure_rot_ahead(Engine* e) {
   if (e->peers2 && e->hl2 && e->rot_list_b[1] && e->rot_changed_b[1]) return GS_OK;
-  const size_t N = e->N;
+  const size_t rows = e->T * e->t_rows, ents = e->T * e->t_ents, lst = (size_t)e->T * e->N;  // (every table's)
   int s = GS_OK;
-  if (!e->peers2) s = dalloc(*e, &e->peers2, N * NB * e->ASZP, 0);
-  if (!s && !e->hl2) s = dalloc(*e, &e->hl2, N * NB, 0);
-  if (!s && !e->rot_list_b[1]) s = dalloc(*e, &e->rot_list_b[1], N, 0);
-  if (!s && !e->rot_changed_b[1]) s = dalloc(*e, &e->rot_changed_b[1], N * NB, 0);
+  if (!e->peers2) s = dalloc(*e, &e->peers2, rows, 0);
+  if (!s && !e->hl2) s = dalloc(*e, &e->hl2, ents, 0);
+  if (!s && !e->rot_list_b[1]) s = dalloc(*e, &e->rot_list_b[1], lst, 0);
+  if (!s && !e->rot_changed_b[1]) s = dalloc(*e, &e->rot_changed_b[1], ents, 0);
   if (s) {
-    dfree(*e, e->peers2, N * NB * e->ASZP);
-    dfree(*e, e->hl2, N * NB);
-    dfree(*e, e->rot_list_b[1], N);
-    dfree(*e, e->rot_changed_b[1], N * NB);
+    dfree(*e, e->peers2, rows);
+    dfree(*e, e->hl2, ents);
+    dfree(*e, e->rot_list_b[1], lst);
+    dfree(*e, e->rot_changed_b[1], ents);
     return s;
   }
   e->rot_list_b[0] = e->rot_list;
@@ -929,8 +1057,8 @@ static int ensure_rot_ahead(Engine* e) {
 static int round_ahead(Engine* e, uint32_t round, bool rec) {
   if (int s = ensure_rot_ahead(e)) return s;
   if (e->rows2_stale) {  // (first round, or the rows changed in place since)
-    HIPC(hipMemcpyAsync(e->peers2, e->peers, (size_t)e->N * NB * e->ASZP * 4, hipMemcpyDeviceToDevice, e->st));
-    HIPC(hipMemcpyAsync(e->hl2, e->hl, (size_t)e->N * NB * 2, hipMemcpyDeviceToDevice, e->st));
+    HIPC(hipMemcpyAsync(e->peers2, e->peers, e->T * e->t_rows * 4, hipMemcpyDeviceToDevice, e->st));
+    HIPC(hipMemcpyAsync(e->hl2, e->hl, e->T * e->t_ents * 2, hipMemcpyDeviceToDevice, e->st));
     e->rows2_stale = false;
     e->rows2_pending = -1;
   }
@@ -1131,30 +1259,39 @@ int gs_read_pruned(gs_engine* eh, uint32_t slot, uint32_t node, uint32_t* fifo_m
   HIPC(hipMemcpyAsync(&bo, e->bucket + org, 1, hipMemcpyDeviceToHost, e->st));
   HIPC(hipStreamSynchronize(e->st));
   const size_t ent = (size_t)node * NB + std::min(bn, bo);
+  const uint32_t t = e->h_stab[slot], asz = e->traj[t].asz;  // the slot's own table
   uint16_t hv = 0;
-  HIPC(hipMemcpy(&hv, e->hl + ent, 2, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(&hv, e->hl + t * e->t_ents + ent, 2, hipMemcpyDeviceToHost));
   const uint32_t head = hv & 0xFF, L = hv >> 8;
   uint32_t out = 0;
   for (uint32_t j = 0; j < L; ++j)
-    if ((m >> ((head + j) % e->ASZ)) & 1u) out |= 1u << j;
+    if ((m >> ((head + j) % asz)) & 1u) out |= 1u << j;
   *fifo_mask = out;
   return GS_OK;
 }
 
 int gs_read_active_sets(gs_engine* eh, uint32_t* peers, uint8_t* len) {
   ENGINE(eh);
+  if (int s_ = one_table(e, "gs_read_active_sets")) return s_;
+  return gs_read_active_sets_traj(eh, 0, peers, len);
+}
+
+int gs_read_active_sets_traj(gs_engine* eh, uint32_t t, uint32_t* peers, uint8_t* len) {
+  ENGINE(eh);
+  if (int s_ = table_check(e, t)) return s_;
   if (int s = check_err(e)) return s;
   const size_t ents = (size_t)e->N * NB;
+  const uint32_t asz = e->traj[t].asz;
   std::vector<uint32_t> rows(ents * e->ASZP);
   std::vector<uint16_t> hl(ents);
-  HIPC(hipMemcpyAsync(rows.data(), e->peers, rows.size() * 4, hipMemcpyDeviceToHost, e->st));
-  HIPC(hipMemcpyAsync(hl.data(), e->hl, ents * 2, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipMemcpyAsync(rows.data(), e->peers + t * e->t_rows, rows.size() * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipMemcpyAsync(hl.data(), e->hl + t * e->t_ents, ents * 2, hipMemcpyDeviceToHost, e->st));
   HIPC(hipStreamSynchronize(e->st));
   for (size_t ent = 0; ent < ents; ++ent) {
     const uint32_t head = hl[ent] & 0xFF, L = hl[ent] >> 8;
     len[ent] = (uint8_t)L;
-    for (uint32_t j = 0; j < e->ASZ; ++j)
-      peers[ent * e->ASZ + j] = j < L ? rows[ent * e->ASZP + (head + j) % e->ASZ] : 0xFFFFFFFFu;
+    for (uint32_t j = 0; j < asz; ++j)
+      peers[ent * asz + j] = j < L ? rows[ent * e->ASZP + (head + j) % asz] : 0xFFFFFFFFu;
   }
   return GS_OK;
 }
@@ -1217,7 +1354,8 @@ int gs_read_pruned_all(gs_engine* eh, uint32_t slot, uint32_t* fifo_mask) {
     HIPC(strided_d2h(e, m.data(), e->mask + slot * e->mso, 4, e->msu * 4, N));
   }
   HIPC(hipMemcpyAsync(b.data(), e->bucket, N, hipMemcpyDeviceToHost, e->st));
-  HIPC(hipMemcpyAsync(hl.data(), e->hl, N * NB * 2, hipMemcpyDeviceToHost, e->st));
+  const uint32_t t = e->h_stab[slot], asz = e->traj[t].asz;  // the slot's own table
+  HIPC(hipMemcpyAsync(hl.data(), e->hl + t * e->t_ents, N * NB * 2, hipMemcpyDeviceToHost, e->st));
   HIPC(hipStreamSynchronize(e->st));
   const uint32_t bo = b[e->slots[slot].origin];
   for (size_t n = 0; n < N; ++n) {
@@ -1225,7 +1363,7 @@ int gs_read_pruned_all(gs_engine* eh, uint32_t slot, uint32_t* fifo_mask) {
     const uint32_t head = hv & 0xFF, L = hv >> 8;
     uint32_t out = 0;
     for (uint32_t j = 0; j < L; ++j)
-      if ((m[n] >> ((head + j) % e->ASZ)) & 1u) out |= 1u << j;
+      if ((m[n] >> ((head + j) % asz)) & 1u) out |= 1u << j;
     fifo_mask[n] = out;
   }
   return GS_OK;
@@ -1420,9 +1558,10 @@ int gs_read_mst(gs_engine* eh, uint32_t slot, uint32_t* parent) {
   std::vector<uint32_t> off(N + 1), src(total + 1);
   std::vector<uint8_t> rh(total + 1);
   if (int s = gs_read_inbound(eh, slot, off.data(), src.data(), rh.data(), total + 1)) return s;
-  std::vector<uint32_t> peers((size_t)N * NB * e->ASZ), fifo(N);
+  const uint32_t tab = e->h_stab[slot], asz = e->traj[tab].asz;  // the slot's own table
+  std::vector<uint32_t> peers((size_t)N * NB * asz), fifo(N);
   std::vector<uint8_t> lens((size_t)N * NB), bkt(N);
-  if (int s = gs_read_active_sets(eh, peers.data(), lens.data())) return s;
+  if (int s = gs_read_active_sets_traj(eh, tab, peers.data(), lens.data())) return s;
   if (int s = gs_read_pruned_all(eh, slot, fifo.data())) return s;
   HIPC(hipMemcpy(bkt.data(), e->bucket, N, hipMemcpyDeviceToHost));
   // index of w in u's take(fanout) list (get_nodes skips pruned peers and the origin)
@@ -1431,7 +1570,7 @@ int gs_read_mst(gs_engine* eh, uint32_t slot, uint32_t* parent) {
     uint32_t t = 0;
     const uint32_t fan = e->h_sfan.empty() ? e->fanout : e->h_sfan[slot];
     for (uint32_t i = 0; i < lens[ent] && t < fan; ++i) {
-      const uint32_t p = peers[ent * e->ASZ + i];
+      const uint32_t p = peers[ent * asz + i];
       if (((fifo[u] >> i) & 1u) || p == org) continue;
       if (p == w) return t;
       ++t;

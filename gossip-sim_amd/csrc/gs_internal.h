@@ -43,6 +43,10 @@ struct MvGeom {
   size_t q_cap = 0, area_cap = 0, rows_cap = 0, pcap = 0;
 };
 struct MvGroup { uint32_t s0, sg, seed0, nseed; };
+// One active-set trajectory table (gs_create_traj): its own ring size and rotation probability,
+// serving the slots [s0, s0 + ns). The device copy (TrajDev) is what the round kernel reads.
+struct TrajTab { uint32_t asz = 0, s0 = 0, ns = 0; double p = 0; };
+struct TrajDev { uint32_t asz, s0; double p; };
 
 struct Engine {
   gs_params prm{};
@@ -59,6 +63,16 @@ struct Engine {
   size_t mso = 0, msu = 1, eso = 0, esu = 1, mask_words = 0;
   uint32_t SP = 0;
   bool fused = false;            // gs_round runs the one-kernel workgroup round
+  // Trajectory tables (gs_create_traj; one for gs_create, which then equals ASZ / prm's probability):
+  // peers / hl / peers2 / hl2 / rot_list_b / rot_changed_b hold T tables back to back (strides
+  // t_rows words, t_ents entries, N list words) and rot_count is [T][2]. All rotation control
+  // (parity, pending clear, buffer swap) stays engine-wide: the tables rotate in lock-step.
+  std::vector<TrajTab> traj;
+  uint32_t T = 1;
+  size_t t_rows = 0, t_ents = 0;
+  uint32_t* stab = nullptr;      // [S] table of each slot (T > 1 only)
+  TrajDev* ttab = nullptr;       // [T] (T > 1 only)
+  std::vector<uint32_t> h_stab;  // host copy of stab (all zero for one table)
   bool inb_valid = true;         // inbound records materialized in HBM (step-wise BFS)
   hipStream_t st = nullptr;
   size_t dev_bytes = 0;
@@ -191,7 +205,8 @@ struct Engine {
 
   size_t rwg_attr_lds = 0;          // dynamic LDS the round kernel was last configured for
   bool rwg_attr_prof = false;       // ... and for which instantiation (phase clocks or not,
-  bool rwg_attr_pf = false;         // per-slot fanouts or not)
+  bool rwg_attr_pf = false;         // per-slot fanouts or not,
+  bool rwg_attr_mt = false;         // several trajectory tables or not)
   // node-range partition (gs_partition.hip): this rank owns node ids [part_lo, part_hi)
   // (= [vlo, vlo + NP)) and the fine bins [part_flo, part_flo + part_fno) of the multi BFS
   bool part_on = false;
@@ -283,7 +298,7 @@ hipError_t launch_prefix_weights(Engine& e);
 hipError_t launch_init_entries(Engine& e);
 hipError_t launch_fail_keys(Engine& e, uint64_t* keys, uint32_t* ids);
 hipError_t launch_scatter_rank(Engine& e, const uint32_t* sorted_ids, uint32_t* rank_out);
-hipError_t launch_clear_slot_masks(Engine& e, uint32_t node, uint32_t bucket, uint32_t bits);
+hipError_t launch_clear_slot_masks(Engine& e, uint32_t table, uint32_t node, uint32_t bucket, uint32_t bits);
 hipError_t launch_bfs(Engine& e, bool record);
 hipError_t launch_bfs_binned(Engine& e, bool record);
 // spin on a host-mapped word the device writes (MV_PENDING until then); checks the stream

@@ -115,8 +115,10 @@ __global__ __launch_bounds__(256) void k_init_entries(const uint8_t* __restrict_
 hipError_t launch_init_entries(Engine& e) {
   const uint32_t total = e.N * NB;
   e.rows2_stale = true;
-  GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_init_entries<A>, dim3(grid_for(total, 256)), dim3(256), 0, e.st,
-                                              e.bucket, e.P, e.IX, e.peers, e.hl, e.N, e.ASZ, e.prm.seed));
+  for (uint32_t t = 0; t < e.T; ++t)  // every trajectory table draws the same INIT streams with its own size
+    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_init_entries<A>, dim3(grid_for(total, 256)), dim3(256), 0, e.st,
+                                                e.bucket, e.P, e.IX, e.peers + t * e.t_rows, e.hl + t * e.t_ents, e.N,
+                                                e.traj[t].asz, e.prm.seed));
   hipError_t r = hipGetLastError();
   return r != hipSuccess ? r : launch_own_rows(e, nullptr, nullptr);
 }
@@ -150,9 +152,12 @@ __global__ void k_clear_slot_masks(size_t mso, size_t msu, uint32_t S, uint32_t 
   const uint32_t b = min((uint32_t)bucket[node], (uint32_t)obkt[o]);
   if (b == bucket_k) mask[o * mso + node * msu] &= ~bits;
 }
-hipError_t launch_clear_slot_masks(Engine& e, uint32_t node, uint32_t bucket_k, uint32_t bits) {
-  hipLaunchKernelGGL(k_clear_slot_masks, dim3(grid_for(e.S, 256)), dim3(256), 0, e.st, e.mso, e.msu, e.S, node,
-                     bucket_k, e.bucket, e.obkt, bits, e.mask);
+// (the slots of trajectory table `table`; its masks are a slot range: with several tables the
+// layout is slot-major)
+hipError_t launch_clear_slot_masks(Engine& e, uint32_t table, uint32_t node, uint32_t bucket_k, uint32_t bits) {
+  const TrajTab& tt = e.traj[table];
+  hipLaunchKernelGGL(k_clear_slot_masks, dim3(grid_for(tt.ns, 256)), dim3(256), 0, e.st, e.mso, e.msu, tt.ns, node,
+                     bucket_k, e.bucket, e.obkt + tt.s0, bits, e.mask + tt.s0 * e.mso);
   return hipGetLastError();
 }
 
@@ -283,8 +288,12 @@ __global__ void k_rotate_clear(size_t mso, size_t msu, uint32_t S, const uint8_t
 }
 
 hipError_t launch_rotate_clear(Engine& e) {
-  hipLaunchKernelGGL(k_rotate_clear, dim3(grid_for((size_t)e.N * e.S, 256, 2048)), dim3(256), 0, e.st, e.mso, e.msu, e.S,
-                     e.bucket, e.obkt, e.rot_list, e.rot_count + e.rot_parity, e.rot_changed, e.mask);
+  for (uint32_t t = 0; t < e.T; ++t) {  // each table's rotation clears its own slots' bits
+    const TrajTab& tt = e.traj[t];
+    hipLaunchKernelGGL(k_rotate_clear, dim3(grid_for((size_t)e.N * tt.ns, 256, 2048)), dim3(256), 0, e.st, e.mso, e.msu,
+                       tt.ns, e.bucket, e.obkt + tt.s0, e.rot_list + (size_t)t * e.N, e.rot_count + 2 * t + e.rot_parity,
+                       e.rot_changed + t * e.t_ents, e.mask + tt.s0 * e.mso);
+  }
   return hipGetLastError();
 }
 
@@ -292,34 +301,41 @@ hipError_t launch_rotate(Engine& e, uint32_t round, bool defer_clear) {
   // GS_ROT_SPLIT=1: the three-launch rotation (decide, entries, own rows) for N > RS_MAX
   static const bool rot_split = std::getenv("GS_ROT_SPLIT") && std::getenv("GS_ROT_SPLIT")[0] == '1';
   const uint32_t par = round & 1u;
-  uint32_t* cnt = e.rot_count + par;
   e.rows2_stale = true;  // (the rows change in place: a later ahead rotation copies them whole first)
-  if (e.rot_cnt_dirty || (e.rot_have_prev && par == e.rot_parity)) {  // not pre-zeroed (rounds not
-                                                                      // consecutive, or after an ahead rotation)
-    e.rot_cnt_dirty = false;
-    hipError_t r = hipMemsetAsync(cnt, 0, sizeof(uint32_t), e.st);
-    if (r != hipSuccess) return r;
-  }
-  if (e.N <= RS_MAX) {
-    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_small<A>, dim3(1), dim3(1024), 0, e.st, e.bucket, e.P, e.IX,
-                                                e.peers, e.hl, e.rot_list, cnt, e.rot_count + (par ^ 1u),
-                                                e.rot_changed, e.N, e.ASZ, e.prm.seed, round,
-                                                e.prm.rotation_probability));
-  } else if (!rot_split) {
-    const uint32_t grid = (e.N + RF_NODES - 1) / RF_NODES;
-    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_fused<A>, dim3(grid), dim3(RF_THREADS), 0, e.st, e.bucket,
-                                                e.P, e.IX, e.peers, e.hl, e.rot_list, cnt, e.rot_count + (par ^ 1u),
-                                                e.rot_changed, e.N, e.ASZ, e.prm.seed, round,
-                                                e.prm.rotation_probability, e.ORW, e.mv_fcls, e.own));
-  } else {
-    hipLaunchKernelGGL(k_rotate_decide, dim3(grid_for(e.N, 4096, 256)), dim3(1024), 0, e.st, e.N, e.prm.seed, round,
-                       e.prm.rotation_probability, e.rot_list, cnt, e.rot_count + (par ^ 1u));
-    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_entries<A>, dim3(grid_for((size_t)e.N * NB, 256, 2048)),
-                                                dim3(256), 0, e.st, e.bucket, e.P, e.IX, e.peers, e.hl, e.rot_list,
-                                                cnt, e.rot_changed, e.N, e.ASZ, e.prm.seed, round));
+  const bool zero_cnt = e.rot_cnt_dirty || (e.rot_have_prev && par == e.rot_parity);  // not pre-zeroed (rounds not
+                                                                                       // consecutive, or after an ahead rotation)
+  e.rot_cnt_dirty = false;
+  for (uint32_t t = 0; t < e.T; ++t) {  // the trajectory tables rotate in lock-step, each with its own size and probability
+    uint32_t* cnt = e.rot_count + 2 * t + par;
+    uint32_t* cnt_other = e.rot_count + 2 * t + (par ^ 1u);
+    uint32_t* peers = e.peers + t * e.t_rows;
+    uint16_t* hl = e.hl + t * e.t_ents;
+    uint32_t* list = e.rot_list + (size_t)t * e.N;
+    uint32_t* changed = e.rot_changed + t * e.t_ents;
+    const uint32_t asz = e.traj[t].asz;
+    const double p = e.traj[t].p;
+    if (zero_cnt) {
+      hipError_t r = hipMemsetAsync(cnt, 0, sizeof(uint32_t), e.st);
+      if (r != hipSuccess) return r;
+    }
+    if (e.N <= RS_MAX) {
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_small<A>, dim3(1), dim3(1024), 0, e.st, e.bucket, e.P, e.IX,
+                                                  peers, hl, list, cnt, cnt_other, changed, e.N, asz, e.prm.seed, round, p));
+    } else if (!rot_split) {
+      const uint32_t grid = (e.N + RF_NODES - 1) / RF_NODES;
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_fused<A>, dim3(grid), dim3(RF_THREADS), 0, e.st, e.bucket,
+                                                  e.P, e.IX, peers, hl, list, cnt, cnt_other, changed, e.N, asz,
+                                                  e.prm.seed, round, p, e.ORW, e.mv_fcls, e.own));
+    } else {
+      hipLaunchKernelGGL(k_rotate_decide, dim3(grid_for(e.N, 4096, 256)), dim3(1024), 0, e.st, e.N, e.prm.seed, round,
+                         p, list, cnt, cnt_other);
+      GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_entries<A>, dim3(grid_for((size_t)e.N * NB, 256, 2048)),
+                                                  dim3(256), 0, e.st, e.bucket, e.P, e.IX, peers, hl, list, cnt, changed,
+                                                  e.N, asz, e.prm.seed, round));
+    }
   }
   if (e.N <= RS_MAX || rot_split) {  // (the fused kernel refreshed its nodes' own rows itself)
-    hipError_t ro = launch_own_rows(e, e.rot_list, cnt);
+    hipError_t ro = launch_own_rows(e, e.rot_list, e.rot_count + par);
     if (ro != hipSuccess) return ro;
   }
   e.rot_parity = par;
@@ -603,12 +619,23 @@ hipError_t launch_bfs(Engine& e, bool record) {
   hipError_t r;
   if (e.bfs_mode == GS_BFS_WORKGROUP) {
     const size_t lds = bfs_wg_lds_bytes(e.N);
-    const uint32_t grid = e.S < 4096 ? e.S : 4096;
-    GS_ASZP_DISPATCH(e.ASZP, {
-      r = hipFuncSetAttribute((const void*)k_bfs_wg<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (r != hipSuccess) return r;
-      hipLaunchKernelGGL(k_bfs_wg<A>, dim3(grid), dim3(256), lds, e.st, a);
-    });
+    for (uint32_t t = 0; t < e.T; ++t) {  // one launch per trajectory table, on its rows and its slot range
+      const TrajTab& tt = e.traj[t];
+      const size_t s0 = tt.s0, p0 = s0 * e.N;
+      BfsArgs b = a;
+      if (e.T > 1) {  // (slot-major layout; inb / PAIRS keep the engine's row stride)
+        b.peers = e.peers + t * e.t_rows; b.hl = e.hl + t * e.t_ents; b.ASZ = tt.asz; b.S = tt.ns;
+        b.origin += s0; b.obkt += s0; b.nfail += s0; if (b.sfan) b.sfan += s0;
+        b.mask += p0; b.hops += p0; b.cnt += p0; b.inb += p0; b.egress += p0; b.egress_acc += p0; b.strand += p0;
+        b.bm += s0 * e.bm_words; b.rs_u32 += s0 * 4; b.rs_ssum += s0; b.rs_hist += s0 * 256;
+      }
+      const uint32_t grid = b.S < 4096 ? b.S : 4096;
+      GS_ASZP_DISPATCH(e.ASZP, {
+        r = hipFuncSetAttribute((const void*)k_bfs_wg<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (r != hipSuccess) return r;
+        hipLaunchKernelGGL(k_bfs_wg<A>, dim3(grid), dim3(256), lds, e.st, b);
+      });
+    }
     return hipGetLastError();
   }
   if (e.bfs_mode == GS_BFS_BINNED) return launch_bfs_binned(e, record);
@@ -656,6 +683,10 @@ struct CpArgs {
   int record;
   size_t PAIRS;
   size_t mso, msu;  // prune-mask strides of (slot, node)
+  // several trajectory tables (else stab is null): slot o's entries are table stab[o]'s
+  const uint32_t* stab;
+  const TrajDev* ttab;
+  size_t t_rows, t_ents;
 };
 
 
@@ -666,12 +697,14 @@ __device__ inline void apply_prune(const CpArgs& a, uint32_t o, uint32_t ob, uin
   if (GS_OOB(u, a.N, a.err, "apply_prune u")) return;
   const uint32_t b = min((uint32_t)a.bucket[u], ob);
   const uint32_t ent = u * NB + b;
-  const uint32_t hv = a.hl[ent];
+  const uint32_t t = a.stab ? a.stab[o] : 0u;
+  const uint32_t asz = a.stab ? a.ttab[t].asz : a.ASZ;
+  const uint32_t hv = (a.hl + t * a.t_ents)[ent];
   const uint32_t head = hv & 0xFF, L = hv >> 8;
-  const uint32_t* row = a.peers + (size_t)ent * a.ASZP;
+  const uint32_t* row = a.peers + t * a.t_rows + (size_t)ent * a.ASZP;
   for (uint32_t j = 0; j < L; ++j) {
     uint32_t slot = head + j;
-    if (slot >= a.ASZ) slot -= a.ASZ;
+    if (slot >= asz) slot -= asz;
     if (row[slot] == v) {
       atomicOr(&a.mask[o * a.mso + u * a.msu], 1u << slot);
       return;
@@ -795,6 +828,7 @@ hipError_t launch_consume_prune(Engine& e, bool consume, bool prune, bool apply,
   a.ingress_acc = e.ingress_acc; a.prune_acc = e.prune_acc; a.record = record ? 1 : 0;
   a.N = e.N; a.S = e.S; a.ASZ = e.ASZ; a.ASZP = e.ASZP; a.capin = e.capin; a.PAIRS = e.PAIRS;
   a.mso = e.mso; a.msu = e.msu;
+  a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents;
   const uint32_t grid = grid_for(e.PAIRS, 256, 8192);
   hipError_t r;
   if (consume && prune && apply) return launch_consume_prune_g(e, record, true, true);  // gs_consume_g.hip

@@ -113,6 +113,13 @@ struct RoundArgs {
   size_t PAIRS;
   int record;
   const uint32_t* sfan;  // [S] per-slot fanouts while they differ (the PF kernels), else null: every slot takes `fanout`
+  // several trajectory tables (the MT kernels; else null): slot o reads table stab[o] -- peers / hl /
+  // rpeers / rhl hold the tables t_rows words / t_ents entries apart, the rotation lists N words,
+  // the changed bits t_ents words and the counters 2 words apart -- with ttab[t]'s size and
+  // probability; rot_on is then the number of tables (one leading rotation workgroup each)
+  const uint32_t* stab;
+  const TrajDev* ttab;
+  size_t t_rows, t_ents;
 };
 
 // Phase clock: thread 0 adds the time since the last mark to phase_clk[ph].
@@ -694,7 +701,8 @@ __device__ void rotate_ahead_wg(const RoundArgs& a, uint32_t* lids) {
     rotate_entry<ASZP>(a.bucket, a.P, a.IX, a.rpeers, a.rhl, lids, a.rchanged, N, a.ASZ, a.seed, a.rround, gid);
 }
 
-template <int ASZP, bool OFF16, int FP, bool PROF, bool PF>  // PF: per-slot fanouts (a.sfan)
+// PF: per-slot fanouts (a.sfan); MT: several trajectory tables (a.stab / a.ttab)
+template <int ASZP, bool OFF16, int FP, bool PROF, bool PF, bool MT>
 __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundArgs a) {
   using PMT = typename std::conditional<(ASZP <= 16), uint16_t, uint32_t>::type;
   using OFFT = typename std::conditional<OFF16, uint16_t, uint32_t>::type;
@@ -721,9 +729,31 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
   uint32_t* scr = reinterpret_cast<uint32_t*>(smem + L.scr) + wid * RWG_SCR;
   const uint32_t W = (N + 31) / 32;
 
-  if (a.rot_on && blockIdx.x == 0) {  // (dispatched first: the rotation overlaps the whole round)
-    rotate_ahead_wg<ASZP>(a, reinterpret_cast<uint32_t*>(smem));
-    return;
+  if constexpr (MT) {
+    // Workgroup t < rot_on rotates table t ahead; the slots' workgroups follow. The table of a
+    // workgroup is uniform: its rebased pointers, ring size and probability stay scalar.
+    if (blockIdx.x < a.rot_on) {
+      const uint32_t t = blockIdx.x;
+      a.peers += t * a.t_rows; a.hl += t * a.t_ents;
+      a.rpeers += t * a.t_rows; a.rhl += t * a.t_ents;
+      a.rlist += (size_t)t * N; a.rcount += 2 * t; a.rchanged += t * a.t_ents;
+      if (a.plist) { a.plist += (size_t)t * N; a.pcount += 2 * t; }
+      a.ASZ = a.ttab[t].asz;
+      a.rp = a.ttab[t].p;
+      rotate_ahead_wg<ASZP>(a, reinterpret_cast<uint32_t*>(smem));
+      return;
+    }
+    const uint32_t t = a.stab[blockIdx.x - a.rot_on];
+    a.peers += t * a.t_rows; a.hl += t * a.t_ents;
+    a.ASZ = a.ttab[t].asz;
+    if (a.rot_count) {  // the pending clear of this table's last rotation
+      a.rot_list += (size_t)t * N; a.rot_count += 2 * t; a.rot_changed += t * a.t_ents;
+    }
+  } else {
+    if (a.rot_on && blockIdx.x == 0) {  // (dispatched first: the rotation overlaps the whole round)
+      rotate_ahead_wg<ASZP>(a, reinterpret_cast<uint32_t*>(smem));
+      return;
+    }
   }
   const uint32_t o = blockIdx.x - a.rot_on;
   const uint32_t org = a.origin[o], ob = a.obkt[o], nf = a.nfail[o];
@@ -1146,25 +1176,31 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
   RWG_MARK(6);
 }
 
-template <int ASZP, bool OFF16, int FP, bool PROF, bool PF>
+template <int ASZP, bool OFF16, int FP, bool PROF, bool PF, bool MT = false>
 static hipError_t launch_rwg_p(Engine& e, const RoundArgs& a, size_t lds) {
-  if (e.rwg_attr_lds != lds || e.rwg_attr_prof != PROF || e.rwg_attr_pf != PF) {
-    hipError_t r = hipFuncSetAttribute((const void*)k_round_wg<ASZP, OFF16, FP, PROF, PF>,
+  if (e.rwg_attr_lds != lds || e.rwg_attr_prof != PROF || e.rwg_attr_pf != PF || e.rwg_attr_mt != MT) {
+    hipError_t r = hipFuncSetAttribute((const void*)k_round_wg<ASZP, OFF16, FP, PROF, PF, MT>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (r != hipSuccess) return r;
     e.rwg_attr_lds = lds;
     e.rwg_attr_prof = PROF;
     e.rwg_attr_pf = PF;
+    e.rwg_attr_mt = MT;
   }
-  hipLaunchKernelGGL((k_round_wg<ASZP, OFF16, FP, PROF, PF>), dim3(e.S + a.rot_on), dim3(RWG_THREADS), lds, e.st, a);
+  hipLaunchKernelGGL((k_round_wg<ASZP, OFF16, FP, PROF, PF, MT>), dim3(e.S + a.rot_on), dim3(RWG_THREADS), lds, e.st, a);
   return hipSuccess;
 }
 
 template <int ASZP, bool OFF16, int FP>
 static hipError_t launch_rwg_fp(Engine& e, const RoundArgs& a, size_t lds) {
   if constexpr (ASZP == 12 && OFF16 && FP == 6) {  // C2's shape: phase clocks available
-    if (a.phase_clk && !a.sfan) return launch_rwg_p<ASZP, OFF16, FP, true, false>(e, a, lds);
+    if (a.phase_clk && !a.sfan && !a.stab) return launch_rwg_p<ASZP, OFF16, FP, true, false>(e, a, lds);
   }
+  // several trajectory tables: the kernels that rebase onto their workgroup's table (the single-table
+  // kernels are unchanged); the per-slot fanouts compose with them
+  if (a.stab)
+    return a.sfan ? launch_rwg_p<ASZP, OFF16, FP, false, true, true>(e, a, lds)
+                  : launch_rwg_p<ASZP, OFF16, FP, false, false, true>(e, a, lds);
   // slots of different fanouts: the kernel that loads its slot's own (the uniform kernel is unchanged)
   if (a.sfan) return launch_rwg_p<ASZP, OFF16, FP, false, true>(e, a, lds);
   return launch_rwg_p<ASZP, OFF16, FP, false, false>(e, a, lds);
@@ -1180,8 +1216,9 @@ static hipError_t launch_rwg(Engine& e, const RoundArgs& a, size_t lds) {
 
 hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_clear, const RotAhead* ra) {
   RoundArgs a;
-  a.rot_on = ra ? 1u : 0u;
-  a.P = e.P; a.IX = e.IX; a.seed = e.prm.seed; a.rp = e.prm.rotation_probability;
+  a.rot_on = ra ? e.T : 0u;  // (one leading rotation workgroup per trajectory table)
+  a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents;
+  a.P = e.P; a.IX = e.IX; a.seed = e.prm.seed; a.rp = e.traj[0].p;
   a.rpeers = ra ? ra->peers2 : nullptr; a.rhl = ra ? ra->hl2 : nullptr;
   a.rlist = ra ? ra->list : nullptr; a.rcount = ra ? ra->count : nullptr; a.rchanged = ra ? ra->changed : nullptr;
   a.plist = ra ? ra->plist : nullptr; a.pcount = ra ? ra->pcount : nullptr;

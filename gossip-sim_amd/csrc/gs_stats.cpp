@@ -204,9 +204,12 @@ int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_
                                     out);
 }
 
-int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
-                               const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
-                               const double* fractions, const uint32_t* fanouts, gs_sim_result** out) {
+// The sims as slots of one engine: with traj (>= 2 tables, the sims already grouped in slot
+// order) a gs_create_traj engine, else the gs_create engine at cfg's size and probability.
+static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                    const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                    const double* fractions, const uint32_t* fanouts, const gs_traj* traj, uint32_t n_traj,
+                    gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
   gs_params prm{};
@@ -217,7 +220,14 @@ int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes,
   prm.device = cfg->device;
   prm.bfs_mode = cfg->bfs_mode;
   gs_engine* e = nullptr;
-  int r = gs_create(&prm, stakes, n, n_sims, &e);
+  int r;
+  if (traj) {
+    prm.active_set_size = 0;  // the capacity: the largest table
+    for (uint32_t t = 0; t < n_traj; ++t) prm.active_set_size = std::max(prm.active_set_size, traj[t].active_set_size);
+    r = gs_create_traj(&prm, stakes, n, n_sims, traj, n_traj, &e);
+  } else {
+    r = gs_create(&prm, stakes, n, n_sims, &e);
+  }
   if (r) return r;
   std::vector<gs_slot> slots(n_sims);
   for (uint32_t i = 0; i < n_sims; ++i) {
@@ -364,6 +374,67 @@ int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes,
 #undef CK
   gs_destroy(e);
   *out = res.release();
+  return GS_OK;
+}
+
+int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                               const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                               const double* fractions, const uint32_t* fanouts, gs_sim_result** out) {
+  return run_sims(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, out);
+}
+
+// A value of active-set size and rotation probability per sim: the sims are grouped by
+// (size, probability) into trajectory tables -- equal pairs need not be adjacent -- run in
+// table order as slots of one engine, and the results come back in sim order.
+int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                            const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                            const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
+                            const double* rotation_probabilities, gs_sim_result** out) {
+  if (!active_set_sizes && !rotation_probabilities)
+    return gs_run_simulations_fanouts(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                                      out);
+  if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
+  *out = nullptr;
+  std::vector<gs_traj> tabs;
+  std::vector<uint32_t> tab_of(n_sims);
+  for (uint32_t i = 0; i < n_sims; ++i) {
+    const uint32_t a = active_set_sizes ? active_set_sizes[i] : cfg->active_set_size;
+    const double p = rotation_probabilities ? rotation_probabilities[i] : cfg->rotation_probability;
+    uint32_t t = 0;
+    while (t < tabs.size() && !(tabs[t].active_set_size == a && tabs[t].rotation_probability == p)) ++t;
+    if (t == tabs.size()) tabs.push_back(gs_traj{a, p, 0});
+    tabs[t].n_slots += 1;
+    tab_of[i] = t;
+  }
+  if (tabs.size() == 1) {  // one value: exactly gs_run_simulations at it
+    gs_sim_config c = *cfg;
+    c.active_set_size = tabs[0].active_set_size;
+    c.rotation_probability = tabs[0].rotation_probability;
+    return gs_run_simulations_fanouts(&c, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                                      out);
+  }
+  std::vector<uint32_t> sim_of;  // slot -> sim, in table order (stable within a table)
+  for (uint32_t t = 0; t < tabs.size(); ++t)
+    for (uint32_t i = 0; i < n_sims; ++i)
+      if (tab_of[i] == t) sim_of.push_back(i);
+  std::vector<uint32_t> orr(n_sims), mi(n_sims), fo(n_sims);
+  std::vector<double> th(n_sims), fr(n_sims);
+  for (uint32_t s = 0; s < n_sims; ++s) {
+    const uint32_t i = sim_of[s];
+    orr[s] = origin_ranks ? origin_ranks[i] : 1;
+    mi[s] = min_ingress ? min_ingress[i] : cfg->min_ingress_nodes;
+    th[s] = thresholds ? thresholds[i] : cfg->prune_stake_threshold;
+    fr[s] = fractions ? fractions[i] : cfg->fraction_to_fail;
+    fo[s] = fanouts ? fanouts[i] : cfg->push_fanout;
+  }
+  gs_sim_result* res = nullptr;
+  const int r = run_sims(cfg, stakes, n, n_sims, orr.data(), mi.data(), th.data(), fr.data(), fanouts ? fo.data() : nullptr,
+                         tabs.data(), (uint32_t)tabs.size(), &res);
+  if (r) return r;
+  std::vector<SimStats> by_sim(n_sims);
+  for (uint32_t s = 0; s < n_sims; ++s) by_sim[sim_of[s]] = std::move(res->sims[s]);
+  res->sims = std::move(by_sim);
+  *out = res;
   return GS_OK;
 }
 

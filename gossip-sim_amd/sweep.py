@@ -21,10 +21,16 @@ with a fanout per slot (run_simulations(fanouts=...)). The reference raises a si
 active-set size to its fanout (gossip_main.rs:809-811), which does change the
 trajectory: `fanout_groups` splits the sweep into the sims that share a size, and
 `run_fanout_sweep` runs each such group as one engine.
+
+`run_traj_sweep` batches the engine-changing sweeps too: an engine may hold several
+active-set trajectory tables (gs_create_traj), one per (size, probability) pair, so a
+rank's whole share of such a sweep runs as one engine (run_simulations(aszs=, rot_probs=))
+when the network fits the workgroup engine (`traj_supported`); otherwise the share runs as
+`run_sweep` does, one engine per value.
 """
 import numpy as np
 
-from . import run_simulations
+from . import run_simulations, traj_supported
 
 F64_NAMES = ["coverage", "rmr", "branching", "hop_mean", "hop_median", "coverage_stats", "rmr_stats",
              "branching_stats", "aggregate_hops", "ldh", "stranded", "stranded_round_mean",
@@ -242,4 +248,69 @@ def run_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_device=
             kw["device"] = device
         res = runner(stakes, n_sims=1, **kw)
         local[i] = {(kind, name): (res.f64(0, name) if kind == "f" else res.u64(0, name)) for kind, name in NAMES}
+    return allreduce_results(local, len(values), group=group, device=comm_device)
+
+
+def traj_tables(aszs, rot_probs):
+    """Table plan of one trajectory-table engine: [(asz, p, sim indices)], one table per distinct
+    (size, probability) pair in order of first occurrence; equal pairs need not be adjacent."""
+    tabs = {}
+    for i, key in enumerate(zip([int(a) for a in aszs], [float(q) for q in rot_probs])):
+        tabs.setdefault(key, []).append(i)
+    return [(a, q, sims) for (a, q), sims in tabs.items()]
+
+
+def traj_units(n_values, world):
+    """The engines of a batched sweep over `world` ranks, as (rank, value indices): the values
+    dealt round-robin (shard), each rank's share one engine; ranks without a value get none."""
+    return [(r, shard(n_values, r, world)) for r in range(world) if shard(n_values, r, world)]
+
+
+_PER_SIM = ("origin_ranks", "min_ingress", "thresholds", "fractions")  # (one value per sim: joined)
+_PER_TABLE = ("fanout", "asz", "p", "n_sims") + _PER_SIM
+
+
+def traj_batchable(cfgs, n_nodes):
+    """Can these run_simulations kwargs (one single-sim dict per value) run as one engine: they
+    may differ only in asz / p / fanout (and the per-sim lists), and the network must fit the
+    workgroup engine at their largest fanout and size."""
+    if not cfgs:
+        return False
+    rest = [{k: v for k, v in c.items() if k not in _PER_TABLE} for c in cfgs]
+    if any(r != rest[0] for r in rest[1:]) or any(c.get("n_sims", 1) != 1 for c in cfgs):
+        return False
+    for k in _PER_SIM:
+        if len({c.get(k) is None for c in cfgs}) > 1:
+            return False
+    return traj_supported(n_nodes, max(c.get("fanout", 6) for c in cfgs), max(c.get("asz", 12) for c in cfgs))[0]
+
+
+def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_device=None, runner=None):
+    """run_sweep with each rank's share as ONE engine of several trajectory tables: the same
+    arguments (values dealt round-robin over the ranks, make_cfg(value) -> kwargs of
+    run_simulations) and bit-identical results. A share that cannot batch (traj_batchable)
+    runs one engine per value, as run_sweep does."""
+    tdist, rank, world = _dist_info(group)
+    runner = runner or run_simulations
+    local = {}
+    mine = shard(len(values), rank, world)
+    cfgs = [dict(make_cfg(values[i])) for i in mine]
+    if len(mine) > 1 and traj_batchable(cfgs, len(stakes)):
+        kw = {k: v for k, v in cfgs[0].items() if k not in _PER_TABLE}
+        for k in _PER_SIM:
+            if cfgs[0].get(k) is not None:
+                kw[k] = [x for c in cfgs for x in c[k]]
+        if device is not None:
+            kw["device"] = device
+        res = runner(stakes, n_sims=len(mine), fanouts=[int(c.get("fanout", 6)) for c in cfgs],
+                     aszs=[int(c.get("asz", 12)) for c in cfgs], rot_probs=[float(c.get("p", 0.013333)) for c in cfgs],
+                     **kw)
+        for j, i in enumerate(mine):
+            local[i] = {(kind, name): (res.f64(j, name) if kind == "f" else res.u64(j, name)) for kind, name in NAMES}
+    else:
+        for i, kw in zip(mine, cfgs):
+            if device is not None:
+                kw["device"] = device
+            res = runner(stakes, n_sims=1, **kw)
+            local[i] = {(kind, name): (res.f64(0, name) if kind == "f" else res.u64(0, name)) for kind, name in NAMES}
     return allreduce_results(local, len(values), group=group, device=comm_device)

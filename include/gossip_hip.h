@@ -24,6 +24,9 @@
  *    (gossip.rs:527-536), never by initialize_gossip, rotation or the weighted shuffle, so
  *    sims that differ only in fanout share the trajectory too, and a push-fanout sweep
  *    batches like the others (its sims with the same active-set size, see sweep.py).
+ *    An engine made by gs_create_traj holds several trajectories (tables), each with its
+ *    own active-set size and rotation probability and its own range of slots, so the
+ *    sims of an active-set-size or rotate-probability sweep batch as well.
  *  - The engine owns all device memory. Inputs are copied at call time; outputs
  *    go to caller buffers with explicit capacities (too small => GS_ERANGE).
  *  - An engine is not re-entrant; use one engine per device per host thread.
@@ -129,6 +132,34 @@ typedef struct gs_engine gs_engine;
 /* --- lifetime --------------------------------------------------------- */
 int gs_create(const gs_params* params, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_slots,
               gs_engine** out);
+/* Several active-set trajectory tables in one engine (an active-set-size or
+ * rotate-probability sweep as one engine): table t has its own ring size and rotation
+ * probability and serves the next n_slots slots -- table 0 the slots [0, n0), table 1 the
+ * next n1, ... fixed at create; the counts must sum to n_slots. params.active_set_size is
+ * the capacity (1..32; row stride, push-mask width and LDS layout are sized by it, as
+ * params.push_fanout sizes the per-slot fanouts) and every table's size is in [1, capacity];
+ * params.rotation_probability is ignored. The seed is engine-wide: tables draw the INIT /
+ * ROTATE / DECIDE streams a gs_create engine with that size and probability draws, so each
+ * slot is bit-identical to its own per-value engine; the FAIL stream is shared. A prune
+ * mask's bits are physical ring slots of the slot's own table. bfs_mode must be
+ * GS_BFS_WORKGROUP or GS_BFS_AUTO (which resolves to WORKGROUP whatever the slot count), and
+ * the network must fit the workgroup engine's LDS (gs_traj_supported, host arithmetic only:
+ * returns 1 / 0, *fused = 1 if gs_round runs the one-kernel round at that capacity), else
+ * GS_EINVAL; so are n_traj == 0, a table with n_slots == 0, a size of 0 or above the
+ * capacity, a probability outside [0, 1]. n_traj == 1 is exactly gs_create with that size
+ * and probability. Everything addressed by slot reads the slot's own table; the calls that
+ * name an entry take the table (the _traj forms below; on an engine with several tables the
+ * un-suffixed ones return GS_EINVAL). No reference interface: the reference builds one
+ * Cluster per value (gossip_main.rs:775-797, 925-951). */
+typedef struct gs_traj {
+  uint32_t active_set_size;      /* 1..params.active_set_size */
+  double rotation_probability;   /* [0,1] */
+  uint32_t n_slots;              /* this table serves the next n_slots slots */
+} gs_traj;
+int gs_create_traj(const gs_params* params, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_slots,
+                   const gs_traj* traj, uint32_t n_traj, gs_engine** out);
+int gs_engine_traj(gs_engine* e, gs_traj* out, uint32_t cap, uint32_t* n_traj); /* reads the tables back */
+int gs_traj_supported(uint32_t n_nodes, uint32_t push_fanout, uint32_t max_active_set_size, int* fused);
 void gs_destroy(gs_engine* e);
 const char* gs_last_error(void);
 /* sha256 prefix (16 hex digits) of the device sources this library was built from; the
@@ -158,6 +189,13 @@ int gs_set_active_set_entry(gs_engine* e, uint32_t node, uint32_t bucket, const 
 int gs_get_active_set_entry(gs_engine* e, uint32_t node, uint32_t bucket, uint32_t* peers, uint32_t cap,
                             uint32_t* len);
 
+/* The same for table t of a gs_create_traj engine (t = 0 on any engine); setting an entry
+ * clears the prune state of that table's slots only. */
+int gs_set_active_set_entry_traj(gs_engine* e, uint32_t t, uint32_t node, uint32_t bucket, const uint32_t* peers,
+                                 uint32_t len);
+int gs_get_active_set_entry_traj(gs_engine* e, uint32_t t, uint32_t node, uint32_t bucket, uint32_t* peers,
+                                 uint32_t cap, uint32_t* len);
+
 /* --- the per-iteration steps: gossip.rs Cluster -------------------------- */
 int gs_fail_nodes(gs_engine* e, const double* fraction_per_slot); /* Cluster::fail_nodes gossip.rs:756 */
 int gs_run_gossip(gs_engine* e);                  /* Cluster::run_gossip gossip.rs:494 */
@@ -186,6 +224,8 @@ int gs_read_pruned(gs_engine* e, uint32_t slot, uint32_t node, uint32_t* fifo_ma
 /* Bulk forms for parity diffing: every entry in FIFO order (peers[(node*25+k)*active_set_size + i],
  * len[node*25+k]); every node's cache for the slot (keys sorted, 96 per node); every node's FIFO prune mask. */
 int gs_read_active_sets(gs_engine* e, uint32_t* peers, uint8_t* len);
+/* table t's entries, with a row stride of that table's own size */
+int gs_read_active_sets_traj(gs_engine* e, uint32_t t, uint32_t* peers, uint8_t* len);
 int gs_read_caches(gs_engine* e, uint32_t slot, uint32_t* num_upserts, uint32_t* len, uint32_t* keys,
                    uint32_t* scores);
 int gs_read_pruned_all(gs_engine* e, uint32_t slot, uint32_t* fifo_mask);
@@ -338,6 +378,15 @@ int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_
 int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_sims,
                                const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                                const double* fractions, const uint32_t* fanouts, gs_sim_result** out);
+/* The same with an active-set size and a rotation probability per sim (an active-set-size or
+ * rotate-probability sweep as one engine): one value per sim, or NULL for cfg's. The sims are
+ * grouped by (size, probability) into the tables of one gs_create_traj engine -- equal pairs
+ * need not be adjacent -- and the results come back in sim order. Both NULL is exactly
+ * gs_run_simulations_fanouts; one distinct pair is that call at the pair's values. */
+int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_sims,
+                            const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                            const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
+                            const double* rotation_probabilities, gs_sim_result** out);
 void gs_result_free(gs_sim_result* r);
 /* Named arrays of a finished sim (same names as the oracle): e.g. "coverage",
  * "rmr", "coverage_stats", "stranded", "hops_hist" ... Returns the element
