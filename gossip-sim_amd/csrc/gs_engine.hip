@@ -185,7 +185,7 @@ static int check_err(Engine* e) {
     return fail(GS_ERANGE, "inbound capacity exceeded: a node received more than " + std::to_string(e->capin) +
                                " pushes in one round; recreate the engine with a larger inbound_capacity");
   if (f & ERR_CACHE) return fail(GS_ERANGE, "received-cache capacity (96 keys) exceeded");
-  if (f & ERR_DEPTH) return fail(GS_ERANGE, "BFS depth exceeds 254 hops (hop counts are u8)");
+  if (f & ERR_DEPTH) return fail(GS_ERANGE, "BFS depth exceeds 253 hops: a node at distance 254 or more was reached (hop counts are u8)");
   if (f & ERR_MV_CAP) {
     std::string what;
     if (f & ERR_MVD_ROWS) what += " level rows";
@@ -945,7 +945,7 @@ static int refuse_part(Engine* e) {
 // Maps a BFS launcher's result: depth beyond u8 hops, a level that never finished, HIP errors.
 static int bfs_result(Engine* e, hipError_t r, const char* what) {
   if (r == hipSuccess) return GS_OK;
-  if (r == hipErrorNotSupported) return fail(GS_ERANGE, "BFS depth exceeds 254 hops (hop counts are u8)");
+  if (r == hipErrorNotSupported) return fail(GS_ERANGE, "BFS depth exceeds 253 hops: a node at distance 254 or more was reached (hop counts are u8)");
   if (r == hipErrorLaunchTimeOut)
     return fail(GS_EHIP, std::string(what) + ": BFS level " + std::to_string(e->bfs_level) +
                              " did not finish within GS_LEVEL_WAIT_S (default 60 s); the device is stuck");
@@ -1675,7 +1675,7 @@ int gs_part_xbfs_expand(gs_engine* eh, uint32_t level, uint64_t* words_to) {
   PARTX(eh);
   if (e->x_group == 0xFFFFFFFFu || level != e->x_level || !words_to)
     return fail(GS_ESTATE, "gs_part_xbfs_expand: begin the group first and take the levels in order");
-  if (level >= 254) return fail(GS_ERANGE, "BFS depth exceeds 254 hops (hop counts are u8)");
+  if (level >= 254) return fail(GS_ERANGE, "BFS depth exceeds 253 hops: a node at distance 254 or more was reached (hop counts are u8)");
   std::vector<uint64_t> w;
   HIPC(mvx_expand(*e, e->x_group, level, e->x_nlocal, w));
   for (uint32_t q = 0; q < e->part_K; ++q) words_to[q] = w[q];
@@ -1756,7 +1756,7 @@ int gs_part_xbfs_expand_async(gs_engine* eh, uint32_t level, uint64_t cap_words,
   PARTX(eh);
   if (e->x_group == 0xFFFFFFFFu || level != e->x_level || !send)
     return fail(GS_ESTATE, "gs_part_xbfs_expand_async: begin the group first and take the levels in order");
-  if (level >= 254) return fail(GS_ERANGE, "BFS depth exceeds 254 hops (hop counts are u8)");
+  if (level >= 254) return fail(GS_ERANGE, "BFS depth exceeds 253 hops: a node at distance 254 or more was reached (hop counts are u8)");
   if (cap_words < mvx_max_bins(*e) || cap_words > 0xFFFFFFF0ull / e->part_K)
     return fail(GS_EINVAL, "gs_part_xbfs_expand_async: a slot must hold every rank's bin headers (and K slots < 2^32 words)");
   if (!e->x_bins_set) {

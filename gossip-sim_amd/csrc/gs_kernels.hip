@@ -656,7 +656,12 @@ hipError_t launch_bfs(Engine& e, bool record) {
       if (*h == 0) return hipGetLastError();
     }
   }
-  return hipErrorNotSupported;  // frontier still non-empty after 254 levels: hop counts no longer fit u8
+  // levels through 253 enqueued (the last poll saw level 252): the hops fit u8 iff level 254 is empty
+  uint32_t* h = e.h_err + 1;
+  if ((r = hipMemcpyAsync(h, e.lvl + 254, 4, hipMemcpyDeviceToHost, e.st)) != hipSuccess) return r;
+  if ((r = hipStreamSynchronize(e.st)) != hipSuccess) return r;
+  if (*h == 0) return hipGetLastError();
+  return hipErrorNotSupported;  // level 254 not empty: hop counts no longer fit u8
 }
 
 // --------------------------------------------- consume / prune (R9-R13) ----

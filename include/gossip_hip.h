@@ -53,6 +53,13 @@ typedef enum gs_status {
 } gs_status;
 
 enum { GS_NUM_BUCKETS = 25, GS_MAX_ACTIVE_SET_SIZE = 32, GS_MAX_NODES = (1 << 24) - 1, GS_HOP_UNREACHED = 0xFF };
+/* The hop limit. Hops are u8 and GS_HOP_UNREACHED marks an unreached node: a round
+ * succeeds if and only if its farthest reached node is at distance <= 253 in every slot
+ * (BFS level 254 is empty; the largest hop an inbound record carries is then 254).
+ * Otherwise the round -- or, where the BFS reports through the deferred error word (the
+ * one-kernel round, the workgroup BFS, the persistent and predicted level loops), the next
+ * gs_sync or readback -- returns GS_ERANGE, in every BFS mode; the engine's results after
+ * that error are unspecified (tests/test_degenerate_graphs.py). */
 /* BFS strategies (results are identical): WORKGROUP = one workgroup per slot with
  * LDS state (small clusters, many slots); LEVEL = level-synchronous over all
  * slots with a global atomic per push; BINNED = level-synchronous,
