@@ -30,6 +30,7 @@ GS_FLAG_WIDE_RECORDS = 16
 GS_FLAG_NO_SMALL_LEVELS = 32
 GS_FLAG_MISPREDICT_LEVELS = 64
 GS_FLAG_FRONTIER_EXCHANGE = 128
+GS_FLAG_TRAJ_MULTI = 256
 HOP_UNREACHED = 0xFF
 B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
 
@@ -111,6 +112,7 @@ EXPORTS = {
                                  C.POINTER(C.c_void_p)]),
     "gs_engine_traj": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "gs_traj_supported": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
+    "gs_traj_multi_supported": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "gs_set_active_set_entry_traj": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                C.c_uint32]),
     "gs_get_active_set_entry_traj": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -211,7 +213,11 @@ def lib():
             raise GsError(-2, f"{LIB_PATH} is missing: run `make -C gossip-sim_amd` (no CPU fallback exists)")
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in EXPORTS.items():
-            f = getattr(L, name)
+            f = getattr(L, name, None)
+            if f is None and os.environ.get("GS_LIB_VARIANT"):
+                continue  # (an A/B build of older sources may predate a symbol; calling it still raises)
+            if f is None:
+                raise GsError(-2, f"{LIB_PATH} does not export {name}: rebuild it (`make -C gossip-sim_amd`)")
             f.restype = res
             f.argtypes = args
         _lib = L
@@ -255,16 +261,26 @@ def traj_supported(n, fanout, max_asz):
     return bool(ok), bool(fused.value)
 
 
+def traj_multi_supported(n, n_slots, fanout, max_asz):
+    """Can a network of n nodes run as a multi-source trajectory-table engine (Engine(...,
+    trajectories=, traj_multi=True, bfs_mode=GS_BFS_MULTI)) of n_slots slots with this push-fanout
+    capacity and largest active-set size. Host arithmetic of the multi-source BFS's geometry
+    rule; needs no device."""
+    return bool(lib().gs_traj_multi_supported(int(n), int(n_slots), int(fanout), int(max_asz)))
+
+
 class Engine:
     """One engine = one device + n_slots sims on one shared active-set trajectory, or, with
     trajectories=[(active_set_size, rotation_probability, n_slots), ...], on several tables:
     table t serves the next n_slots slots (their counts sum to the engine's), the capacity is
-    the largest size, and `active_set_size` / `rotation_probability` are unused."""
+    the largest size, and `active_set_size` / `rotation_probability` are unused. traj_multi=True
+    (GS_FLAG_TRAJ_MULTI) lets the tables live on the multi-source BFS: bfs_mode=GS_BFS_MULTI at
+    any size it supports, AUTO beyond the workgroup engine."""
 
     def __init__(self, stakes, n_slots, *, fanout=6, active_set_size=12, rotation_probability=0.013333, seed=0,
                  device=0, bfs_mode=GS_BFS_AUTO, inbound_capacity=0, profile=False, split_round=False,
                  narrow_wave_path=False, binned_all_levels=False, wide_records=False, no_small_levels=False,
-                 mispredict_levels=False, frontier_exchange=False, part=None, trajectories=None):
+                 mispredict_levels=False, frontier_exchange=False, part=None, trajectories=None, traj_multi=False):
         L = lib()
         if trajectories is not None:
             if part is not None:
@@ -281,7 +297,8 @@ class Engine:
                    (GS_FLAG_BINNED_ALL_LEVELS if binned_all_levels else 0) |
                    (GS_FLAG_WIDE_RECORDS if wide_records else 0) | (GS_FLAG_NO_SMALL_LEVELS if no_small_levels else 0) |
                    (GS_FLAG_MISPREDICT_LEVELS if mispredict_levels else 0) |
-                   (GS_FLAG_FRONTIER_EXCHANGE if frontier_exchange else 0))
+                   (GS_FLAG_FRONTIER_EXCHANGE if frontier_exchange else 0) |
+                   (GS_FLAG_TRAJ_MULTI if traj_multi else 0))
         h = C.c_void_p()
         if trajectories is not None:
             arr = (Traj * max(1, len(trajectories)))(*[Traj(a, q, k) for a, q, k in trajectories])

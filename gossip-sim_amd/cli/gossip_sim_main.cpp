@@ -99,7 +99,10 @@ void usage() {
       "  --engine-plan PATH   write one line per engine: device, simulations, active-set size, fanouts\n"
       "  --batch-sweeps       run an active-set-size, rotate-probability or push-fanout sweep as ONE engine per\n"
       "                       device (an active-set table per value) instead of one engine per value; a plan\n"
-      "                       line then lists active-set-size, fanouts and rotation-probability per simulation\n"
+      "                       line then lists active-set-size, fanouts and rotation-probability per simulation.\n"
+      "                       Networks beyond the workgroup engine (about 16,000 nodes) fall back to one engine\n"
+      "                       per value, unless --bfs-mode 4 is given: then the tables live on the multi-source\n"
+      "                       BFS at any node count it supports (one engine per device)\n"
       "  --influx-file PATH   write the Influx series (influx_db.rs) as line protocol to PATH\n"
       "  --influx-time-base NS  reproducible Influx timestamps NS + 1000 k (default: wall clock)\n"
       "gossip-sim write-accounts --account-file PATH --synthetic N [--num-nodes K] [--zero-stakes] [-f]");
@@ -408,7 +411,15 @@ int main(int argc, char** argv) {
     if (traj) {
       uint64_t fmax = 1, amax = 1;
       for (const auto& q : params) { fmax = std::max(fmax, q.gossip_push_fanout); amax = std::max(amax, q.gossip_active_set_size); }
-      if (amax > GS_MAX_ACTIVE_SET_SIZE ||
+      if (c.bfs_mode == GS_BFS_MULTI) {  // the tables on the multi-source BFS: any node count it supports
+        if (amax > GS_MAX_ACTIVE_SET_SIZE ||
+            !gs_traj_multi_supported((uint32_t)stakes.size(), (uint32_t)std::min<uint64_t>(num_sims, 0xFFFFFFFFu),
+                                     (uint32_t)std::min<uint64_t>(fmax, 0xFFFFFFFFu), (uint32_t)amax)) {
+          gsrep::log_info(stderr, TMAIN, "--batch-sweeps: " + std::to_string(stakes.size()) + " nodes at active-set size " +
+                                             std::to_string(amax) + " do not fit the multi-source table engine; planning one engine per value");
+          traj = false;
+        }
+      } else if (amax > GS_MAX_ACTIVE_SET_SIZE ||
           !gs_traj_supported((uint32_t)stakes.size(), (uint32_t)std::min<uint64_t>(fmax, 0xFFFFFFFFu), (uint32_t)amax, nullptr)) {
         gsrep::log_info(stderr, TMAIN, "--batch-sweeps: " + std::to_string(stakes.size()) + " nodes at active-set size " +
                                            std::to_string(amax) + " do not fit the workgroup engine; planning one engine per value");

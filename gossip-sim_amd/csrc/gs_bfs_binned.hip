@@ -786,8 +786,13 @@ __global__ void k_own_rows(const uint8_t* __restrict__ bucket, const uint32_t* _
 hipError_t launch_own_rows(Engine& e, const uint32_t* list, const uint32_t* count) {
   if (!e.own) return hipSuccess;
   const uint32_t grid = (uint32_t)std::min<size_t>((e.N + 255) / 256, 2048);
-  GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_own_rows<A>, dim3(grid), dim3(256), 0, e.st, e.bucket, e.peers,
-                                              e.hl, list, count, e.N, e.ORW, e.mv_fcls, e.own));
+  // every trajectory table's own rows from its own entries (a list is the rotation's: table t's
+  // rotating nodes and their count lie t * N words and 2 t counters after table 0's)
+  for (uint32_t t = 0; t < e.T; ++t)
+    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_own_rows<A>, dim3(grid), dim3(256), 0, e.st, e.bucket,
+                                                e.peers + t * e.t_rows, e.hl + t * e.t_ents,
+                                                list ? list + (size_t)t * e.N : nullptr, count ? count + 2 * t : nullptr,
+                                                e.N, e.ORW, e.mv_fcls, e.own + t * e.own_ts));
   return hipGetLastError();
 }
 

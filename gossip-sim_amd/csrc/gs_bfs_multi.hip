@@ -56,7 +56,8 @@ namespace {
 // the rows cost more than the records; 1,024-entry slices make 4x fewer rows (C5 BFS
 // 9.36 -> 6.95 ms per round) while at C4's 245 bins 256-entry slices stay faster (730 vs
 // 768 us).
-template <int ASZP, uint32_t XT, bool PF>
+// MT: several trajectory tables (mv_expand_entry)
+template <int ASZP, uint32_t XT, bool PF, bool MT = false>
 __global__ __launch_bounds__(XT) void k_mv_expand(MvArgs a, uint32_t d, uint32_t pi, const uint2* __restrict__ q0,
                                                   const uint2* __restrict__ q1) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(XT) void k_mv_expand(MvArgs a, uint32_t d, uint32_t
     return;
   }
   const uint32_t tid = threadIdx.x, nb = a.nbc, BSC = a.BSC, UB = a.UB, BPm = (1u << BSC) - 1;
-  mv_slots_load<PF>(a, S, tid, XT);
+  mv_slots_load<PF, MT>(a, S, tid, XT);
   uint32_t* hist = reinterpret_cast<uint32_t*>(smem);  // [nb] + scan words
   unsigned long long* stage = reinterpret_cast<unsigned long long*>(smem + mv_hist_bytes(nb));  // [XT * ASZP]
   for (uint32_t w = blockIdx.x; w < G; w += gridDim.x) {
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(XT) void k_mv_expand(MvArgs a, uint32_t d, uint32_t
 #pragma unroll
     for (int s = 0; s < ASZP; ++s) { row[s] = 0; acc[s] = 0; }
     const uint32_t i = w * XT + tid;
-    if (i < qn) mv_expand_entry<ASZP, true, PF>(a, qcur[i], S, row, acc, u);
+    if (i < qn) mv_expand_entry<ASZP, true, PF, MT>(a, qcur[i], S, row, acc, u);
     // every LDS atomic after every load: each record's rank within its coarse bin
     uint32_t rk[ASZP];
 #pragma unroll
@@ -131,9 +132,12 @@ __host__ __device__ inline size_t mv_apply_lds_bytes(uint32_t BSC) {
 }
 
 
+// MT: several trajectory tables (a node's new slots split by table first, mv_parts_to)
+template <bool MT>
 __global__ __launch_bounds__(MV_AT) void k_mv_apply(MvArgs a, uint32_t d, uint32_t pi, uint2* __restrict__ q0,
                                                    uint2* __restrict__ q1) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t* gtt = MT ? a.gt : nullptr;
   if (pi != MV_NOPAIR) d = a.dpair[pi];
   const uint32_t qn = d < 254 ? a.lvl[d] : 0u;
   uint2* __restrict__ qnxt = (d & 1) ? q0 : q1;
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(MV_AT) void k_mv_apply(MvArgs a, uint32_t d, uint32
   uint32_t cntp = 0;
   for (uint32_t i = tid; i < nv; i += MV_AT) {
     const uint32_t nw = visL[i] & ~vis0[i];
-    if (nw) cntp += mv_parts(gt, v0 + i, nw, a.bucket[v0 + i], nullptr, 0);
+    if (nw) cntp += mv_parts<MT>(gt, v0 + i, nw, a.bucket[v0 + i], nullptr, 0, gtt);
   }
   const uint32_t incl = wave_incl_scan(cntp);
   if ((tid & 63) == 63) ctl[8 + (tid >> 6)] = incl;
@@ -274,7 +278,7 @@ __global__ __launch_bounds__(MV_AT) void k_mv_apply(MvArgs a, uint32_t d, uint32
     if (!nw) continue;
     const uint32_t v = v0 + i;
     a.vis[v] = visL[i];
-    pos += mv_parts(gt, v, nw, a.bucket[v], qnxt, pos);
+    pos += mv_parts<MT>(gt, v, nw, a.bucket[v], qnxt, pos, gtt);
   }
   mark(19);
 }
@@ -302,7 +306,7 @@ enum : uint32_t { MV_HEAD = 0, MV_TAIL = 1, MV_POLL = 2 };  // small-kernel mode
 //            to host-mapped memory (hprof) for the next round's prediction;
 //   MV_POLL  from level d0 while levels have at most a.small entries (the polled loop).
 // Every mode reports (level, entries) where it stopped in hstate.
-template <int ASZP, bool PF>
+template <int ASZP, bool PF, bool MT = false>
 __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uint32_t d0, uint32_t pi,
                                                     uint2* __restrict__ q0, uint2* __restrict__ q1,
                                                     uint32_t* __restrict__ hstate, const uint2* __restrict__ seeds,
@@ -315,7 +319,8 @@ __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uin
   __shared__ uint32_t gt[GT_WORDS], cnt_s;
   const uint32_t tid = threadIdx.x;
   const bool LP = a.fno <= MV_SMALL_LP;  // (uniform; beyond, device-scope atomics on a.pused)
-  mv_slots_load<PF>(a, S, tid, MV_ST);
+  const uint32_t* gtt = MT ? a.gt : nullptr;  // (several trajectory tables: the group's table words)
+  mv_slots_load<PF, MT>(a, S, tid, MV_ST);
   for (uint32_t i = tid; i < GT_WORDS; i += MV_ST) gt[i] = a.gt[i];
   uint32_t d = mode == MV_TAIL ? a.dpair[pi] : d0;
   bool inL = false;  // the current level's entries [0, MV_SQ) are in qL[d & 1]
@@ -329,7 +334,8 @@ __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uin
     if (tid < nseed) {
       const uint2 sd = seeds[tid];  // distinct origins (vis was cleared before this kernel)
       qL[0][tid] = sd;
-      a.vis[sd.x & 0xFFFFFFu] = sd.y;
+      if constexpr (MT) atomic_or_wg(&a.vis[sd.x & 0xFFFFFFu], sd.y);  // (one seed per (origin, table))
+      else a.vis[sd.x & 0xFFFFFFu] = sd.y;
     }
     inL = true;
     __syncthreads();  // (full: the seeds' vis stores land before any vis atomic)
@@ -365,7 +371,7 @@ __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uin
       uint32_t row[ASZP], acc[ASZP], u = 0;
 #pragma unroll
       for (int s = 0; s < ASZP; ++s) { row[s] = 0; acc[s] = 0; }
-      if (i < qn) mv_expand_entry<ASZP, true, PF>(a, inL && i < MV_SQ ? ql[i] : qg[i], S, row, acc, u);
+      if (i < qn) mv_expand_entry<ASZP, true, PF, MT>(a, inL && i < MV_SQ ? ql[i] : qg[i], S, row, acc, u);
       if (a.pclk && i0 == 0) {  // (profiling only: wait for the entry's loads)
         uint32_t x = 0;
 #pragma unroll
@@ -400,13 +406,13 @@ __global__ __launch_bounds__(MV_ST) void k_mv_small(MvArgs a, uint32_t mode, uin
             atomicOr(a.err, ERR_MV_CAP | ERR_MVD_POOL);
         }
         if (nw) {  // this thread's first arrivals at w (another thread may add more bits to w)
-          const uint32_t n = mv_parts(gt, w, nw, bw[s], nullptr, 0);
+          const uint32_t n = mv_parts<MT>(gt, w, nw, bw[s], nullptr, 0, gtt);
           const uint32_t base = atomicAdd(&cnt_s, n);
           if ((size_t)base + n <= a.q_cap) {
-            mv_parts_to(gt, w, nw, bw[s], [&](uint32_t k, uint2 x) {
+            mv_parts_to<MT>(gt, w, nw, bw[s], [&](uint32_t k, uint2 x) {
               if (base + k < MV_SQ) qln[base + k] = x;
               else qgn[base + k] = x;
-            });
+            }, gtt);
           } else {
             atomicOr(a.err, ERR_MV_CAP | ERR_MVD_Q);
           }
@@ -1024,7 +1030,26 @@ static uint32_t ceil_log2(size_t x) {
   return l;
 }
 
-void mv_geometry(uint32_t N, uint32_t S, uint32_t ASZ, uint32_t ASZP, MvGeom& g) {
+// Pool records per node (average over a fine bin) of an engine of several trajectory tables:
+// slots of different tables share no push record, so a group's estimate is the sum over the
+// tables present in it of the single-table estimate (size x min(slots in the group, 4)); the
+// largest group's counts. A group of t one-slot tables gives the sum of their sizes, about
+// (size / fanout) times the ~fanout x t records a node receives on average.
+size_t mv_traj_rpn(const std::vector<TrajTab>& traj, uint32_t S, uint32_t GW) {
+  size_t best = 0;
+  for (uint32_t s0 = 0; s0 < S; s0 += GW) {
+    const uint32_t s1 = std::min(S, s0 + GW);
+    size_t sum = 0;
+    for (const TrajTab& t : traj) {
+      const uint32_t lo = std::max(s0, t.s0), hi = std::min(s1, t.s0 + t.ns);
+      if (lo < hi) sum += (size_t)t.asz * std::min<size_t>(hi - lo, 4);
+    }
+    best = std::max(best, sum);
+  }
+  return best + 16;
+}
+
+void mv_geometry(uint32_t N, uint32_t S, uint32_t ASZ, uint32_t ASZP, MvGeom& g, size_t rpn_tab) {
   (void)ASZP;
   g.UB = std::max(1u, ceil_log2(N));
   g.BSC = std::min(13u, std::max(6u, g.UB > 8 ? g.UB - 8 : 0u));   // ~256 coarse bins
@@ -1042,11 +1067,14 @@ void mv_geometry(uint32_t N, uint32_t S, uint32_t ASZ, uint32_t ASZP, MvGeom& g)
   g.GW = std::min(28u, std::min((64u - g.UB - g.BSC) & ~3u, (64u - g.UB - g.BSF - 8) & ~3u));
   g.TW = g.nbc + 2;
   const size_t sg = std::min<size_t>(S, g.GW);
-  g.q_cap = (size_t)N * std::min<size_t>(sg, 26) + 64;
+  // entries per node and level: the own bucket's plus one per lower origin bucket (<= 26); with
+  // several tables one such set per table, and never more than the group's slots
+  g.q_cap = (size_t)N * std::min<size_t>(sg, rpn_tab ? MV_GW_MAX : 26) + 64;
   g.XT = g.nbc >= MV_XT_WIDE && mv_hist_bytes(g.nbc) + (size_t)MV_XT_L * ASZP * 8 <= 160 * 1024 ? MV_XT_L : MV_XT;
   g.rows_cap = (g.q_cap + g.XT - 1) / g.XT + 1;
   g.area_cap = std::min<size_t>(g.rows_cap * g.XT * ASZ, 0xFFFFFFF0u);  // expand slice w's run at w * XT * ASZ
   size_t rpn = (size_t)ASZ * std::min<size_t>(sg, 4) + 16;  // pool records per node (average over a bin)
+  if (rpn_tab) rpn = rpn_tab;  // (several trajectory tables: mv_traj_rpn)
   // A record carries at least one slot's push, and a (slot, node) receives at most the inbound
   // capacity (64 by default), so 64 * sg records per node cannot overflow. Networks small enough
   // that such a pool stays below 8 MiB take it: on a few hundred nodes a group of distinct
@@ -1065,56 +1093,14 @@ bool mv_supported(const MvGeom& g, uint32_t ASZP) {
          g.GW >= 4;
 }
 
-// Host-side slot groups (contiguous ranges of <= GW slots) and their tables.
+// Host-side slot groups (contiguous ranges of <= GW slots) and their tables (gs_mv_groups.h).
 void mv_build_groups(Engine& e, const std::vector<uint32_t>& origins, const std::vector<uint8_t>& obkt,
                      const std::vector<uint8_t>& bucket, std::vector<uint32_t>& gtab, std::vector<uint2>& seeds) {
-  const uint32_t GW = e.mv.GW;
-  const uint32_t ng = (e.S + GW - 1) / GW;
-  gtab.assign((size_t)ng * GT_STRIDE, 0);
+  std::vector<MvSeed> sd;
+  mv_groups_build(e.S, e.mv.GW, origins.data(), obkt.data(), bucket.data(), e.T > 1 ? e.h_stab.data() : nullptr, gtab,
+                  sd, e.mv_groups);
   seeds.clear();
-  e.mv_groups.clear();
-  for (uint32_t g = 0; g < ng; ++g) {
-    const uint32_t s0 = g * GW, sg = std::min(GW, e.S - s0);
-    uint32_t* t = gtab.data() + (size_t)g * GT_STRIDE;
-    {  // origin -> slot mask, open addressing with two probes (mv_origin_slots)
-      uint32_t* ot = t + GT_OT;
-      for (uint32_t i = 0; i < 128; ++i) ot[2 * i] = 0xFFFFFFFFu;
-      bool ok = true;
-      for (uint32_t j = 0; j < sg; ++j) {
-        const uint32_t o = origins[s0 + j], h0 = mv_ohash(o), h1 = (h0 + 1) & 127u;
-        const uint32_t h = (ot[2 * h0] == o || ot[2 * h0] == 0xFFFFFFFFu) ? h0
-                           : (ot[2 * h1] == o || ot[2 * h1] == 0xFFFFFFFFu) ? h1 : 128u;
-        if (h == 128u) { ok = false; continue; }
-        ot[2 * h] = o;
-        ot[2 * h + 1] |= 1u << j;
-      }
-      t[GT_OTOK] = ok ? 1u : 0u;
-    }
-    for (uint32_t k = 0; k < (uint32_t)NB; ++k)
-      for (uint32_t j = 0; j < sg; ++j)
-        if (obkt[s0 + j] >= k) t[GT_OWN + k] |= 1u << j;
-    uint32_t nobs = 0;
-    for (uint32_t j = 0; j < sg; ++j) {
-      uint32_t i = 0;
-      while (i < nobs && t[GT_OBV + i] != obkt[s0 + j]) ++i;
-      if (i == nobs) { t[GT_OBV + i] = obkt[s0 + j]; ++nobs; }
-      t[GT_OBM + i] |= 1u << j;
-    }
-    t[GT_NOBS] = nobs;
-    const uint32_t seed0 = (uint32_t)seeds.size();
-    for (uint32_t j = 0; j < sg; ++j) {  // one seed entry per distinct origin; its own entry
-      const uint32_t org = origins[s0 + j];
-      size_t i = seed0;
-      while (i < seeds.size() && (seeds[i].x & 0xFFFFFFu) != org) ++i;
-      if (i == seeds.size()) seeds.push_back(make_uint2(org | ((uint32_t)bucket[org] << 24), 0u));
-      seeds[i].y |= 1u << j;
-    }
-    t[GT_NSEED] = (uint32_t)seeds.size() - seed0;
-    t[GT_SEED] = seed0;
-    t[GT_S0] = s0;
-    t[GT_SG] = sg;
-    e.mv_groups.push_back({s0, sg, seed0, t[GT_NSEED]});
-  }
+  for (const MvSeed& x : sd) seeds.push_back(make_uint2(x.x, x.y));
 }
 
 // After the failure counts change: per-slot failure classes and the per-node table.
@@ -1148,6 +1134,10 @@ MvArgs mv_args(Engine& e, const MvGroup& gr, uint32_t g) {
   a.vis = e.mv_vis; a.lvl = e.lvl; a.hlvl = e.mv_hlvl_dev; a.T = e.mv_T; a.area = e.mv_area; a.ctr = e.mv_ctr;
   a.dpair = e.mv_dpair; a.hprof = nullptr; a.clear_vis = 0;
   a.sfan = e.fvar ? e.sfan : nullptr;
+  // several trajectory tables: the MT kernels, which read every slot's fanout (the table
+  // engine keeps e.sfan from create on)
+  a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents; a.own_ts = e.own_ts;
+  if (a.stab) a.sfan = e.sfan;
   a.pool = e.mv_pool; a.pused = e.mv_pused;
   a.N = e.N; a.SP = e.SP; a.ASZ = e.ASZ; a.fanout = e.fanout; a.capin = e.capin; a.s0 = gr.s0; a.Sg = gr.sg;
   a.UB = e.mv.UB; a.BSC = e.mv.BSC; a.BSF = e.mv.BSF; a.nbc = e.mv.nbc; a.nbf = e.mv.nbf; a.TW = e.mv.TW;
@@ -1217,7 +1207,16 @@ hipError_t level_empty(Engine& e, uint32_t d, bool& empty) {
 // One expand launch (slices of e.mv.XT entries).
 static void launch_expand(Engine& e, const MvArgs& a, uint32_t d, uint32_t pi, size_t lds_x, uint32_t xgrid) {
   // (a.sfan: the slots' fanouts differ -- the PF kernels; the uniform ones are unchanged by them)
-  if (e.mv.XT == MV_XT_L) {
+  // (a.stab: several trajectory tables -- the MT kernels, which always take per-slot fanouts)
+  if (a.stab) {
+    if (e.mv.XT == MV_XT_L) {
+      GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT_L, true, true>), dim3(xgrid), dim3(MV_XT_L),
+                                                    lds_x, e.st, a, d, pi, e.mv_q[0], e.mv_q[1]));
+    } else {
+      GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT, true, true>), dim3(xgrid), dim3(MV_XT), lds_x,
+                                                    e.st, a, d, pi, e.mv_q[0], e.mv_q[1]));
+    }
+  } else if (e.mv.XT == MV_XT_L) {
     if (a.sfan) {
       GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_expand<A, MV_XT_L, true>), dim3(xgrid), dim3(MV_XT_L), lds_x,
                                                     e.st, a, d, pi, e.mv_q[0], e.mv_q[1]));
@@ -1234,10 +1233,19 @@ static void launch_expand(Engine& e, const MvArgs& a, uint32_t d, uint32_t pi, s
   }
 }
 
+// One apply launch (pair pi, or level d with MV_NOPAIR).
+static void launch_apply(Engine& e, const MvArgs& a, uint32_t d, uint32_t pi, size_t lds_a, uint32_t agrid) {
+  if (a.stab) hipLaunchKernelGGL(k_mv_apply<true>, dim3(agrid), dim3(MV_AT), lds_a, e.st, a, d, pi, e.mv_q[0], e.mv_q[1]);
+  else hipLaunchKernelGGL(k_mv_apply<false>, dim3(agrid), dim3(MV_AT), lds_a, e.st, a, d, pi, e.mv_q[0], e.mv_q[1]);
+}
+
 // The small-level kernel (one workgroup, k_mv_small).
 static void launch_small_levels(Engine& e, const MvArgs& a, uint32_t mode, uint32_t d0, uint32_t pi,
                                 const uint2* seeds, uint32_t nseed, uint32_t seq, size_t lds_s) {
-  if (a.sfan) {
+  if (a.stab) {  // several trajectory tables: the MT kernel (always with per-slot fanouts)
+    GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_small<A, true, true>), dim3(1), dim3(MV_ST), lds_s, e.st, a, mode,
+                                                  d0, pi, e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
+  } else if (a.sfan) {
     GS_ASZP_DISPATCH_V(e.ASZP, hipLaunchKernelGGL((k_mv_small<A, true>), dim3(1), dim3(MV_ST), lds_s, e.st, a, mode, d0,
                                                   pi, e.mv_q[0], e.mv_q[1], e.mv_hstate_dev, seeds, nseed, seq));
   } else {
@@ -1287,7 +1295,7 @@ static hipError_t mv_group_polled(Engine& e, MvArgs& a, const MvGroup& gr, uint3
       }
       hl[d] = MV_PENDING;
       launch_expand(e, a, d, MV_NOPAIR, lds_x, xgrid);
-      hipLaunchKernelGGL(k_mv_apply, dim3(agrid), dim3(MV_AT), lds_a, e.st, a, d, MV_NOPAIR, e.mv_q[0], e.mv_q[1]);
+      launch_apply(e, a, d, MV_NOPAIR, lds_a, agrid);
       if (d >= dl + lag) {
         uint32_t x = 0;
         e.bfs_level = d - lag;
@@ -1315,9 +1323,15 @@ static hipError_t mv_attrs(Engine& e) {
       if (r == hipSuccess)
         r = hipFuncSetAttribute(wide ? (const void*)k_mv_expand<A, MV_XT_L, true> : (const void*)k_mv_expand<A, MV_XT, true>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
+      if (r == hipSuccess && e.T > 1)  // (several trajectory tables)
+        r = hipFuncSetAttribute(wide ? (const void*)k_mv_expand<A, MV_XT_L, true, true>
+                                     : (const void*)k_mv_expand<A, MV_XT, true, true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
     });
     if (r != hipSuccess) return r;
-    if ((r = hipFuncSetAttribute((const void*)k_mv_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)))
+    if ((r = hipFuncSetAttribute((const void*)k_mv_apply<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)))
+      return r;
+    if ((r = hipFuncSetAttribute((const void*)k_mv_apply<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)))
       return r;
     if ((r = hipFuncSetAttribute((const void*)k_mv_gather, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g)))
       return r;
@@ -1327,6 +1341,9 @@ static hipError_t mv_attrs(Engine& e) {
       r = hipFuncSetAttribute((const void*)k_mv_small<A, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
       if (r == hipSuccess)
         r = hipFuncSetAttribute((const void*)k_mv_small<A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
+      if (r == hipSuccess && e.T > 1)
+        r = hipFuncSetAttribute((const void*)k_mv_small<A, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds_s);
     });
     if (r != hipSuccess) return r;
     e.mv_attr_set = true;
@@ -1413,7 +1430,7 @@ hipError_t launch_bfs_multi(Engine& e, bool record, bool consume) {
         const uint32_t gp = (uint32_t)(((size_t)pl + e.mv.XT - 1) / e.mv.XT);
         const uint32_t xg = full_grid ? xgrid : std::min<uint32_t>(xgrid, std::max<uint32_t>(16, gp + gp / 4 + 8));
         launch_expand(e, a, 0u, i, lds_x, xg);
-        hipLaunchKernelGGL(k_mv_apply, dim3(agrid), dim3(MV_AT), lds_a, e.st, a, 0u, i, e.mv_q[0], e.mv_q[1]);
+        launch_apply(e, a, 0u, i, lds_a, agrid);
       }
       const uint32_t seq = ++e.mv_seq ? e.mv_seq : ++e.mv_seq;  // (never 0)
       launch_small_levels(e, a, MV_TAIL, 0u, npairs, nullptr, 0u, seq, lds_s);
@@ -1537,7 +1554,7 @@ hipError_t mvx_apply(Engine& e, uint32_t g, uint32_t d, const unsigned long long
   a.xrows = K;
   const size_t lds_a = mv_apply_lds_bytes(e.mv.BSC);
   const uint32_t agrid = ((e.mv.nbc + 7) / 8) * 8;
-  hipLaunchKernelGGL(k_mv_apply, dim3(agrid), dim3(MV_AT), lds_a, e.st, a, d, MV_NOPAIR, e.mv_q[0], e.mv_q[1]);
+  launch_apply(e, a, d, MV_NOPAIR, lds_a, agrid);
   if ((r = hipMemcpyAsync(e.h_err + 1, e.lvl + d + 1, 4, hipMemcpyDeviceToHost, e.st))) return r;
   if ((r = hipStreamSynchronize(e.st))) return r;
   n_next = e.h_err[1];
@@ -1575,7 +1592,7 @@ hipError_t mvx_apply_async(Engine& e, uint32_t g, uint32_t d, const unsigned lon
   a.xrows = K;
   const size_t lds_a = mv_apply_lds_bytes(e.mv.BSC);
   const uint32_t agrid = ((e.mv.nbc + 7) / 8) * 8;
-  hipLaunchKernelGGL(k_mv_apply, dim3(agrid), dim3(MV_AT), lds_a, e.st, a, d, MV_NOPAIR, e.mv_q[0], e.mv_q[1]);
+  launch_apply(e, a, d, MV_NOPAIR, lds_a, agrid);
   return hipGetLastError();
 }
 

@@ -164,7 +164,9 @@ __device__ inline uint2 ld_entry(const uint2* p) {
 // slots in FIFO order), then failed peers burn their slot (gossip.rs:527-541); the slot's
 // egress byte. Lane j < ASZP returns ring slot j's record (its peer and the slots that push
 // to it) in row[0] / acc[0].
-template <int ASZP, uint32_t LW, bool PF>
+// MT: several trajectory tables -- the entry's table (one for all its slots, so for all LW lanes)
+// gives the own row, the peers row, the ring head / length and the ring size.
+template <int ASZP, uint32_t LW, bool PF, bool MT>
 __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, const MvSlots& S, uint32_t (&row)[ASZP],
                                       uint32_t (&acc)[ASZP], uint32_t& u) {
   constexpr int TQ = (mv_orw<ASZP>() - ASZP) / 4;
@@ -173,8 +175,10 @@ __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, co
   const uint32_t k = ent.x >> 24, M = valid ? ent.y : 0u;
   if (GS_OOB(u, a.N, a.err, "pbfs wide node")) u = 0;
   const bool inM = (M >> j) & 1u;
+  uint32_t tsz = 0, tb = 0;  // (MT) the entry's table and its ring size
+  if constexpr (MT) tb = mv_slot_table(S, M, tsz);
   uint32_t rw[ASZP];
-  const uint32_t* orow = a.own + (size_t)u * a.ORW;
+  const uint32_t* orow = (MT ? a.own + tb * a.own_ts : a.own) + (size_t)u * a.ORW;
   load_row<ASZP>(orow, rw);
   uint32_t tail[4 * TQ];
   {
@@ -192,15 +196,15 @@ __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, co
     for (int s = 0; s < ASZP; ++s) fc[s] = (tail[1 + s / 4] >> (8 * (s % 4))) & 0xFFu;
   } else {  // an origin of lower bucket: entry min(bucket[u], bucket[origin])
     const uint32_t ent_i = u * NB + k;
-    hv = a.hl[ent_i];
-    load_row<ASZP>(a.peers + (size_t)ent_i * ASZP, rw);
+    hv = (MT ? a.hl + tb * a.t_ents : a.hl)[ent_i];
+    load_row<ASZP>((MT ? a.peers + tb * a.t_rows : a.peers) + (size_t)ent_i * ASZP, rw);
 #pragma unroll
     for (int s = 0; s < ASZP; ++s) fc[s] = a.any_fail ? a.fcls[rw[s]] : 0xFFu;
   }
   uint32_t tk = 0;
   if (inM) {
-    tk = taken_slots<ASZP>(rw, hv & 0xFF, hv >> 8, a.ASZ, pm, S.sorg[j], PF ? S.sfan[j] : a.fanout);
-    const uint32_t f = S.sfk[j];
+    tk = taken_slots<ASZP>(rw, hv & 0xFF, hv >> 8, MT ? tsz : a.ASZ, pm, S.sorg[j], PF ? S.sfan[j] : a.fanout);
+    const uint32_t f = MT ? S.sfk[j] & 0xFFu : S.sfk[j];
     if (f) {  // failed peers burn their fanout slot (gossip.rs:538-541)
 #pragma unroll
       for (int s = 0; s < ASZP; ++s)
@@ -221,7 +225,7 @@ __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, co
   acc[0] = ma;
 }
 
-template <int ASZP, bool PF>
+template <int ASZP, bool PF, bool MT = false>
 __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   // (everything in the dynamic LDS: no static shared memory shifts its 16-byte base)
@@ -250,7 +254,8 @@ __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
   uint2* gq = p.gq + (size_t)g * p.gq_cap;
   auto node_of = [&](uint32_t li) { return ((((li >> BSF) << GL) + g) << BSF) | (li & BPm); };
 
-  mv_slots_load<PF>(a, S, tid, PB_T);
+  const uint32_t* gtt = MT ? a.gt : nullptr;  // (several trajectory tables: the group's table words, mv_parts_to)
+  mv_slots_load<PF, MT>(a, S, tid, PB_T);
   for (uint32_t i = tid; i < GT_WORDS; i += PB_T) gt[i] = a.gt[i];
   for (uint32_t i = tid; i < NO; i += PB_T) {
     visL[i] = 0;
@@ -260,7 +265,7 @@ __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
   }
   for (uint32_t i = tid; i < FPW; i += PB_T) fcur[i] = 0;
   lds_barrier();
-  if (tid == 0) {  // level 0: the group's seeds (distinct origins, their own entries) this workgroup owns
+  if (tid == 0) {  // level 0: the group's seeds (distinct (origin, table) pairs, their own entries) this workgroup owns
     uint32_t n = 0;
     for (uint32_t i = 0; i < p.nseed; ++i) {
       const uint2 sd = p.seeds[i];
@@ -320,9 +325,9 @@ __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
       const uint32_t i = c0 + tid;
       if (wide) {
         const uint32_t e = tid / LW;
-        pb_expand_wide<ASZP, LW, PF>(a, e < ne ? ent[e] : make_uint2(0u, 0u), e < ne, S, row, acc, u);
+        pb_expand_wide<ASZP, LW, PF, MT>(a, e < ne ? ent[e] : make_uint2(0u, 0u), e < ne, S, row, acc, u);
       } else if (tid < CH && i < ne) {
-        mv_expand_entry<ASZP, true, PF>(a, i < PB_EC ? ent[i] : ld_entry(&gq[i - PB_EC]), S, row, acc, u);
+        mv_expand_entry<ASZP, true, PF, MT>(a, i < PB_EC ? ent[i] : ld_entry(&gq[i - PB_EC]), S, row, acc, u);
       }
       if (trc && c0 == 0) {  // (trace: thread 0's own entry, its loads and stores drained)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -422,7 +427,7 @@ __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
     uint32_t cntp = 0;
     for (uint32_t k = tid; k < nt; k += PB_T) {
       const uint32_t li = tl[k];
-      cntp += mv_parts(gt, node_of(li), visL[li] & ~visP[li], bk[li], nullptr, 0);
+      cntp += mv_parts<MT>(gt, node_of(li), visL[li] & ~visP[li], bk[li], nullptr, 0, gtt);
     }
     const uint32_t incl = wave_incl_scan(cntp);
     if ((tid & 63) == 63) hist[tid >> 6] = incl;
@@ -441,11 +446,11 @@ __global__ __launch_bounds__(PB_T, 1) void k_mv_pbfs(PbArgs p) {
       const uint32_t li = tl[k];
       const uint32_t nw = visL[li] & ~visP[li];
       visP[li] = visL[li];
-      pos += mv_parts_to(gt, node_of(li), nw, bk[li], [&](uint32_t j, uint2 x) {
+      pos += mv_parts_to<MT>(gt, node_of(li), nw, bk[li], [&](uint32_t j, uint2 x) {
         const uint32_t q = pos + j;
         if (q < PB_EC) ent[q] = x;
         else if (q < PB_EC + p.gq_cap) st_entry(&gq[q - PB_EC], x);
-      });
+      }, gtt);
     }
     // entries in LDS; those in the workgroup's global region (sc1) are drained first
     if (tnew > PB_EC) __syncthreads();
@@ -549,7 +554,8 @@ bool pb_setup(Engine& e) {
   if (lds > 160 * 1024) return false;
   e.pb_G = G; e.pb_GL = GL; e.pb_FPW = FPW; e.pb_LB = LB; e.pb_CH = CH; e.pb_lds = lds;
   // slices per level: every workgroup's entries in chunks of CH
-  const size_t maxparts = std::min<size_t>(m.GW, 26) + 1;
+  // (entries per node and level: <= 26 for one table; several tables split by table first, <= GW)
+  const size_t maxparts = std::min<size_t>(m.GW, e.T > 1 ? MV_GW_MAX : 26) + 1;
   e.pb_gq_cap = (uint32_t)std::min<size_t>((size_t)NO * maxparts, 0xFFFFFFF0u);
   e.pb_rows_cap = (uint32_t)std::min<size_t>((m.q_cap + CH - 1) / CH + G + 1, 0xFFFFFFF0u);
   e.pb_area_cap = (size_t)e.pb_rows_cap * CH * e.ASZ;
@@ -580,6 +586,9 @@ hipError_t launch_bfs_pers(Engine& e, const MvArgs& a, const MvGroup& gr) {
                               (int)e.pb_lds);
       if (r == hipSuccess)
         r = hipFuncSetAttribute((const void*)k_mv_pbfs<A, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)e.pb_lds);
+      if (r == hipSuccess && e.T > 1)  // (several trajectory tables)
+        r = hipFuncSetAttribute((const void*)k_mv_pbfs<A, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)e.pb_lds);
     });
     if (r != hipSuccess) return r;
@@ -613,7 +622,7 @@ hipError_t launch_bfs_pers(Engine& e, const MvArgs& a, const MvGroup& gr) {
   }
   if ((r = hipMemsetAsync(e.pb_blk, 0, PB_BLK_WORDS * 4, e.st))) return r;
   static const bool twice = std::getenv("GS_PB_TWICE") && std::getenv("GS_PB_TWICE")[0] == '1';  // (diagnostics)
-  if (twice) {
+  if (twice && !a.stab) {
     PbArgs q = p;
     q.tr = nullptr;
     if (a.sfan) {
@@ -623,7 +632,9 @@ hipError_t launch_bfs_pers(Engine& e, const MvArgs& a, const MvGroup& gr) {
     }
     if ((r = hipMemsetAsync(e.pb_blk, 0, PB_BLK_WORDS * 4, e.st))) return r;
   }
-  if (a.sfan) {  // the slots' fanouts differ: the PF kernel (the uniform one is unchanged by it)
+  if (a.stab) {  // several trajectory tables: the MT kernel (always with per-slot fanouts)
+    GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A, true, true>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, p));
+  } else if (a.sfan) {  // the slots' fanouts differ: the PF kernel (the uniform one is unchanged by it)
     GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A, true>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, p));
   } else {
     GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL((k_mv_pbfs<A, false>), dim3(e.pb_G), dim3(PB_T), e.pb_lds, e.st, p));

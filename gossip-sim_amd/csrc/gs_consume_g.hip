@@ -124,7 +124,7 @@ __device__ inline void apply_prune(const CgArgs& a, uint32_t o, uint32_t ob, uin
   const uint32_t bu = a.bucket[u], k = min(bu, ob);
   uint32_t row[ASZP], hv;
   uint32_t asz = a.ASZ;
-  if (a.stab) {  // (workgroup engines only: no own rows)
+  if (a.stab) {  // (several tables: the slot's own table; a.own is null then, no own-row shortcut)
     const uint32_t t = a.stab[o];
     const uint32_t ent = u * NB + k;
     asz = a.ttab[t].asz;
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_prune(CgArgs a) {
 hipError_t launch_consume_prune_g(Engine& e, bool record, bool consume, bool zero_slot_prunes) {
   CgArgs a;
   a.stake = e.stake; a.bucket = e.bucket; a.peers = e.peers; a.hl = e.hl; a.origin = e.origin; a.obkt = e.obkt;
-  a.own = e.own; a.ORW = e.ORW;
+  a.own = e.T > 1 ? nullptr : e.own; a.ORW = e.ORW;  // (several tables: no own-row shortcut, apply_prune reads the slot's table)
   a.min_ingress = e.min_ingress; a.thr = e.thr; a.prank = e.prank; a.by_prank = e.by_prank; a.pstake = e.pstake; a.pinfo = e.pinfo;
   a.cnt = e.cnt; a.inb = e.inb; a.cmeta = e.cmeta; a.ckey = e.ckey; a.prune_round = e.prune_round;
   a.slot_prunes = e.slot_prunes; a.mask = e.mask; a.ingress_acc = e.ingress_acc; a.prune_acc = e.prune_acc;

@@ -290,8 +290,8 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   // (expand slice w writes its records at w * XT * ASZ and a T row holds that place as a u32:
   // the whole area must stay below 2^32 records -- ~16M nodes x 20-slot groups x a wide
   // active set would not)
-  const bool mv_area_ok = (double)e->mv.rows_cap * e->mv.XT * e->ASZ <= (double)0xFFFFFFF0u;
-  const bool mv_ok = mv_supported(e->mv, e->ASZP) && mv_area_ok;
+  bool mv_area_ok = (double)e->mv.rows_cap * e->mv.XT * e->ASZ <= (double)0xFFFFFFF0u;
+  bool mv_ok = mv_supported(e->mv, e->ASZP) && mv_area_ok;
   if (part) {  // a partition rank runs the multi-source BFS over its replicated tables
     if (mode != GS_BFS_AUTO && mode != GS_BFS_MULTI) {
       destroy_engine(e);
@@ -318,13 +318,26 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
     e->vlo = lo;
     e->PAIRS = (size_t)e->NP * n_slots;
   }
-  if (traj) {  // several tables: the workgroup engine only (its slots already run concurrently)
-    if (mode != GS_BFS_AUTO && mode != GS_BFS_WORKGROUP) {
+  if (traj) {  // several tables: the workgroup engine (its slots already run concurrently), or with
+               // GS_FLAG_TRAJ_MULTI the multi-source BFS (gs_create_traj resolved AUTO)
+    const bool multi = (prm->flags & GS_FLAG_TRAJ_MULTI) && mode == GS_BFS_MULTI;
+    if (mode != GS_BFS_AUTO && mode != GS_BFS_WORKGROUP && !multi) {
       destroy_engine(e);
       return fail(GS_EINVAL, "gs_create_traj: trajectory tables need bfs_mode GS_BFS_WORKGROUP (or AUTO); the other "
                              "BFS strategies hold one active-set table");
     }
-    mode = GS_BFS_WORKGROUP;
+    if (!multi) mode = GS_BFS_WORKGROUP;
+    if (multi) {
+      if (n_traj >= 65536) {
+        destroy_engine(e);
+        return fail(GS_EINVAL, "gs_create_traj: the multi-source BFS holds at most 65,535 trajectory tables");
+      }
+      // the capacities that assume one table, from the tables: entries per node and level, pool
+      // records per node (slots of different tables share neither)
+      mv_geometry(n, n_slots, e->ASZ, e->ASZP, e->mv, mv_traj_rpn(e->traj, n_slots, e->mv.GW));
+      mv_area_ok = (double)e->mv.rows_cap * e->mv.XT * e->ASZ <= (double)0xFFFFFFF0u;
+      mv_ok = mv_supported(e->mv, e->ASZP) && mv_area_ok;
+    }
   }
   // AUTO, measured: MULTI 2.6 vs BINNED 3.6 ms per C4 round (13 slots); at 10M nodes MULTI wins
   // from 2 slots (4.86 vs 5.26 ms); round 5, with expand grids sized from the level profile, at
@@ -389,7 +402,9 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
     // reads one HBM line per entry instead of two half-used ones
     const uint32_t row_words = ((e->ASZP + 1 + e->ASZP / 4) + 3) & ~3u;
     const char* nl = std::getenv("GS_MV_NO_LINE");
-    if (row_words + e->SP <= 32 && !(nl && nl[0] == '1')) {
+    // (several trajectory tables: a node has one own row per table but one mask word per slot,
+    // so the masks keep their own node-major array)
+    if (row_words + e->SP <= 32 && !(nl && nl[0] == '1') && e->T == 1) {
       e->mv_line = true;
       e->msu = 32;
     }
@@ -482,8 +497,18 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
     if (const char* fu = std::getenv("GS_MV_FUSED"); fu && fu[0] == '1') e->mv_fused = true;
     const uint32_t row_words = ((e->ASZP + 1 + e->ASZP / 4) + 3) & ~3u;  // row, meta, peers' failure classes
     e->ORW = e->mv_line ? 32 : row_words;
-    ALLOC(e->own, N * e->ORW, 0);
+    e->own_ts = N * e->ORW;
+    ALLOC(e->own, e->T * e->own_ts, 0);  // [T][N][ORW]: every trajectory table's own rows
     if (e->mv_line) e->mask = e->own + row_words;
+    if (e->T > 1) {  // the several-table kernels read every slot's fanout (the PF forms)
+      e->h_sfan.assign(S, e->fanout);
+      ALLOC(e->sfan, S, 0);
+      if (hipMemcpyAsync(e->sfan, e->h_sfan.data(), S * 4, hipMemcpyHostToDevice, e->st) != hipSuccess ||
+          hipStreamSynchronize(e->st) != hipSuccess) {
+        destroy_engine(e);
+        return fail(GS_EHIP, "slot fanout upload");
+      }
+    }
     ALLOC(e->mv_vis, N, 0);
     ALLOC(e->mv_q[0], g.q_cap, 0);
     ALLOC(e->mv_q[1], g.q_cap, 0);
@@ -625,6 +650,21 @@ int gs_traj_supported(uint32_t n_nodes, uint32_t push_fanout, uint32_t max_activ
   return 1;
 }
 
+// Host arithmetic of the multi-source table engine's rule (no device): the bin geometry at the
+// capacity and the several-table frontier bound (mv_geometry), its LDS and group-width limits
+// (mv_supported) and the level area below 2^32 records.
+int gs_traj_multi_supported(uint32_t n_nodes, uint32_t n_slots, uint32_t push_fanout, uint32_t max_active_set_size) {
+  if (n_nodes < 2 || n_nodes > GS_MAX_NODES || n_slots < 1 || push_fanout < 1 || max_active_set_size < 1 ||
+      max_active_set_size > GS_MAX_ACTIVE_SET_SIZE)
+    return 0;
+  if ((uint64_t)n_nodes * n_slots >= (1ull << 32)) return 0;
+  const uint32_t aszp = (max_active_set_size + 3) & ~3u;
+  MvGeom g;
+  mv_geometry(n_nodes, n_slots, max_active_set_size, aszp, g, 1);
+  const bool area_ok = (double)g.rows_cap * g.XT * max_active_set_size <= (double)0xFFFFFFF0u;
+  return mv_supported(g, aszp) && area_ok ? 1 : 0;
+}
+
 int gs_create_traj(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots, const gs_traj* traj,
                    uint32_t n_traj, gs_engine** out) {
   if (!prm || !stakes || !out || !traj) return fail(GS_EINVAL, "null argument");
@@ -645,11 +685,19 @@ int gs_create_traj(const gs_params* prm, const uint64_t* stakes, uint32_t n, uin
   }
   if (sum != n_slots) return fail(GS_EINVAL, "gs_create_traj: the tables' n_slots must sum to n_slots");
   gs_params p = *prm;
-  if (p.bfs_mode != GS_BFS_AUTO && p.bfs_mode != GS_BFS_WORKGROUP)
-    return fail(GS_EINVAL, "gs_create_traj: trajectory tables need bfs_mode GS_BFS_WORKGROUP (or AUTO); the other "
-                           "BFS strategies hold one active-set table");
-  p.bfs_mode = GS_BFS_WORKGROUP;
-  if (!gs_traj_supported(n, p.push_fanout ? p.push_fanout : 1, p.active_set_size, nullptr) && n >= 2 && n <= GS_MAX_NODES)
+  const bool wg_ok = gs_traj_supported(n, p.push_fanout ? p.push_fanout : 1, p.active_set_size, nullptr) != 0;
+  if (p.flags & GS_FLAG_TRAJ_MULTI) {  // the table bank on the multi-source BFS too
+    if (p.bfs_mode != GS_BFS_AUTO && p.bfs_mode != GS_BFS_WORKGROUP && p.bfs_mode != GS_BFS_MULTI)
+      return fail(GS_EINVAL, "gs_create_traj: trajectory tables need bfs_mode GS_BFS_WORKGROUP or GS_BFS_MULTI (or AUTO); "
+                             "the level, binned and hybrid BFS hold one active-set table");
+    if (p.bfs_mode == GS_BFS_AUTO) p.bfs_mode = wg_ok ? GS_BFS_WORKGROUP : GS_BFS_MULTI;
+  } else {
+    if (p.bfs_mode != GS_BFS_AUTO && p.bfs_mode != GS_BFS_WORKGROUP)
+      return fail(GS_EINVAL, "gs_create_traj: trajectory tables need bfs_mode GS_BFS_WORKGROUP (or AUTO); the other "
+                             "BFS strategies hold one active-set table");
+    p.bfs_mode = GS_BFS_WORKGROUP;
+  }
+  if (p.bfs_mode == GS_BFS_WORKGROUP && !wg_ok && n >= 2 && n <= GS_MAX_NODES)
     return fail(GS_EINVAL, "gs_create_traj: the network does not fit the workgroup engine's LDS (gs_traj_supported)");
   if (n_traj == 1) {  // one table: exactly the engine gs_create makes with that size and probability
     p.active_set_size = traj[0].active_set_size;

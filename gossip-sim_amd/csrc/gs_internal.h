@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/gossip_hip.h"
+#include "gs_mv_groups.h"
 
 namespace gs {
 
@@ -33,16 +34,12 @@ struct BinGeom {
 // Geometry of the multi-source frontier BFS (gs_bfs_multi.hip): bins of 2^BS nodes,
 // level records u64 = src | node-in-coarse-bin << UB | slot mask << (UB + BSC); pool records
 // src | node-in-fine-bin << UB | hop << (UB + BSF) | slot mask << (UB + BSF + 8); slot groups of <= GW.
-constexpr uint32_t GT_WORDS = 96;  // per-group table words (the part the level kernels copy to LDS)
-// ... followed by the group's origin -> slot-mask hash (128 (id, mask) pairs, two probes;
-// word GT_OTOK of the table = 1 when every origin is in it): a group's table is GT_STRIDE words
-constexpr uint32_t GT_OT = GT_WORDS, GT_OTOK = 94, GT_STRIDE = GT_WORDS + 256;
+// (the groups' tables -- GT_WORDS, GT_STRIDE and the words between -- and MvGroup: gs_mv_groups.h)
 struct MvGeom {
   uint32_t UB = 0, BSC = 0, BSF = 0, nbc = 0, nbf = 0, GW = 0, TW = 0, gcap = 0, gcap_c = 0;
   uint32_t XT = 256;  // frontier entries per expand slice (256, or 1,024 for wide T rows)
   size_t q_cap = 0, area_cap = 0, rows_cap = 0, pcap = 0;
 };
-struct MvGroup { uint32_t s0, sg, seed0, nseed; };
 // One active-set trajectory table (gs_create_traj): its own ring size and rotation probability,
 // serving the slots [s0, s0 + ns). The device copy (TrajDev) is what the round kernel reads.
 struct TrajTab { uint32_t asz = 0, s0 = 0, ns = 0; double p = 0; };
@@ -157,7 +154,8 @@ struct Engine {
   bool mv_attr_set = false;
   uint32_t bfs_level = 0;  // the level loop's current level (reported when a level wait times out)
   bool mv_diag = false;  // GS_MV_DIAG=1
-  bool mv_line = false;   // multi: prune masks live in the row table's node lines (msu = 32)
+  bool mv_line = false;   // multi: prune masks live in the row table's node lines (msu = 32; one table only)
+  size_t own_ts = 0;      // multi: words between two trajectory tables' own rows (N * ORW)
   bool mv_vis_clean = true;  // mv_vis is all zero (allocated zeroed; a clearing gather ran last)
   bool mv_fused = false;  // gs_round: gather, then k_cg_consume; GS_MV_FUSED=1: fused gather + consume (slower at C4)
   // direction-optimizing BFS over the round's push graph (GS_BFS_HYBRID, gs_bfs_hybrid.hip);
@@ -321,7 +319,11 @@ hipError_t level_empty(Engine& e, uint32_t d, bool& empty);
 hipError_t launch_bfs_level_step(Engine& e, bool record, uint32_t d, uint32_t qmin, uint32_t qmax);
 void bin_geometry(uint32_t N, size_t PAIRS, uint32_t fcap, BinGeom& g, bool allow_narrow);
 bool bin_supported(const BinGeom& g, uint32_t fcap);
-void mv_geometry(uint32_t N, uint32_t S, uint32_t ASZ, uint32_t ASZP, MvGeom& g);
+// tables (several trajectory tables): slots of different tables share no frontier entry and no push
+// record, so a node takes up to min(Sg, 28) entries per level and `rpn_tab` pool records on average
+// (mv_traj_rpn); 0: one table
+void mv_geometry(uint32_t N, uint32_t S, uint32_t ASZ, uint32_t ASZP, MvGeom& g, size_t rpn_tab = 0);
+size_t mv_traj_rpn(const std::vector<TrajTab>& traj, uint32_t S, uint32_t GW);
 bool mv_supported(const MvGeom& g, uint32_t ASZP);
 uint32_t mv_kept_bins(const Engine& e);
 void mv_build_groups(Engine& e, const std::vector<uint32_t>& origins, const std::vector<uint8_t>& obkt,

@@ -152,8 +152,8 @@ __global__ void k_clear_slot_masks(size_t mso, size_t msu, uint32_t S, uint32_t 
   const uint32_t b = min((uint32_t)bucket[node], (uint32_t)obkt[o]);
   if (b == bucket_k) mask[o * mso + node * msu] &= ~bits;
 }
-// (the slots of trajectory table `table`; its masks are a slot range: with several tables the
-// layout is slot-major)
+// (the slots of trajectory table `table`; its masks are a slot range in either layout: slot-major
+// on the workgroup engine, node-major with the masks in their own array on the multi-source BFS)
 hipError_t launch_clear_slot_masks(Engine& e, uint32_t table, uint32_t node, uint32_t bucket_k, uint32_t bits) {
   const TrajTab& tt = e.traj[table];
   hipLaunchKernelGGL(k_clear_slot_masks, dim3(grid_for(tt.ns, 256)), dim3(256), 0, e.st, e.mso, e.msu, tt.ns, node,
@@ -325,7 +325,8 @@ hipError_t launch_rotate(Engine& e, uint32_t round, bool defer_clear) {
       const uint32_t grid = (e.N + RF_NODES - 1) / RF_NODES;
       GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_fused<A>, dim3(grid), dim3(RF_THREADS), 0, e.st, e.bucket,
                                                   e.P, e.IX, peers, hl, list, cnt, cnt_other, changed, e.N, asz,
-                                                  e.prm.seed, round, p, e.ORW, e.mv_fcls, e.own));
+                                                  e.prm.seed, round, p, e.ORW, e.mv_fcls,
+                                                  e.own ? e.own + t * e.own_ts : nullptr));
     } else {
       hipLaunchKernelGGL(k_rotate_decide, dim3(grid_for(e.N, 4096, 256)), dim3(1024), 0, e.st, e.N, e.prm.seed, round,
                          p, list, cnt, cnt_other);

@@ -15,8 +15,7 @@ constexpr uint32_t MV_AT = 1024;      // apply threads
 constexpr uint32_t MV_GT = 512;       // gather threads
 constexpr uint32_t MV_SEG = 1024;     // T rows per apply chunk
 constexpr uint32_t MV_NOPAIR = 0xFFFFFFFFu;  // expand / apply: the level is the kernel argument d
-constexpr uint32_t GT_OWN = 0, GT_NOBS = 25, GT_OBV = 26, GT_OBM = 58, GT_NSEED = 90, GT_SEED = 91, GT_S0 = 92,
-                   GT_SG = 93;
+static_assert(MV_NB == (uint32_t)NB, "gs_mv_groups.h's entry count");
 
 struct MvArgs {
   const uint8_t* bucket;
@@ -75,6 +74,13 @@ struct MvArgs {
   // per-slot fanouts [S] while they differ (the PF kernels; `fanout` is then the longest of them), else
   // null: every slot takes `fanout`
   const uint32_t* sfan;
+  // several trajectory tables (the MT kernels; else stab is null and the fields below unused):
+  // slot o's entries are table stab[o]'s, of ring size ttab[t].asz; table t's peers / hl / own rows
+  // lie t * t_rows / t * t_ents / t * own_ts words (entries) after table 0's. ASZ stays the
+  // capacity: the stride of a slice's run in the record area.
+  const uint32_t* stab;
+  const TrajDev* ttab;
+  size_t t_rows, t_ents, own_ts;
 };
 
 // Entry b of expand run (T row) w: b = 0 the run's base in the record area, b = 1 + c its
@@ -127,8 +133,6 @@ __host__ __device__ inline size_t mv_hist_bytes(uint32_t nbins) { return 4 * (si
 // --------------------------------------------------------------- expand ----
 constexpr uint32_t MV_SG4 = 7;  // slot quads per group (GW <= 28)
 
-__host__ __device__ inline uint32_t mv_ohash(uint32_t x) { return (x * 0x9E3779B1u) >> 25; }
-
 // The group's slots as the expand reads them (LDS): origins, failure classes, the slots
 // that may take the shared-prefix path (pz: all, or none when the origin hash is
 // incomplete, so that every slot takes the per-slot path), the origin -> slot-mask hash of
@@ -137,6 +141,9 @@ __host__ __device__ inline uint32_t mv_ohash(uint32_t x) { return (x * 0x9E3779B
 // fanouts (a.sfan): each slot's fanout, and per ring position i the slots with fanout > i
 // (fgt[i]: position i is inside their prefix) and with fanout == i (feq[i]: position i is
 // their stand-in when their origin sits inside their prefix).
+// With several trajectory tables (the MT kernels) sfk[j] also carries slot j's table: its ring
+// size in bits 8..15 and its index from bit 16 (mv_slot_table; the struct keeps its size, so
+// the single-table kernels keep their LDS).
 struct MvSlots {
   uint32_t sorg[32], sfk[32];
   uint2 otab[128];
@@ -146,11 +153,16 @@ struct MvSlots {
 };
 
 // (no barrier: the caller's first __syncthreads publishes S)
-template <bool PF = false>
+template <bool PF = false, bool MT = false>
 __device__ inline void mv_slots_load(const MvArgs& a, MvSlots& S, uint32_t tid, uint32_t nth) {
   if (tid < a.Sg) {
     S.sorg[tid] = a.origin[a.s0 + tid];
-    S.sfk[tid] = a.fk[a.s0 + tid];
+    uint32_t w = a.fk[a.s0 + tid];
+    if constexpr (MT) {
+      const uint32_t t = a.stab[a.s0 + tid];
+      w |= (a.ttab[t].asz << 8) | (t << 16);
+    }
+    S.sfk[tid] = w;
   }
   const uint2* ot = reinterpret_cast<const uint2*>(a.gt + GT_OT);
   for (uint32_t i = tid; i < 128; i += nth) S.otab[i] = ot[i];
@@ -205,7 +217,18 @@ constexpr int mv_orw() { return ((ASZP + 1 + ASZP / 4) + 3) & ~3; }
 // slots with prune bits at u run the per-slot selection, which a wave executes for the
 // union of its lanes' slots. Plain slots' push counts come from bit-sliced counters.
 // EG: write the egress bytes of the entry's slots. PF: per-slot fanouts (a.sfan; S.sfan, S.fgt, S.feq)
-template <int ASZP, bool EG = true, bool PF = false>
+// MT: several trajectory tables. An entry's slots share ONE table (mv_parts_to and the seeds split
+// by table), found from the mask's lowest slot: its own row, peers row, ring head / length and
+// ring size are that table's, so the shared prefix of the plain slots stays one prefix.
+// (the one-table instantiations read a.own / a.peers / a.hl / a.ASZ exactly as before: every
+// table value below is behind a compile-time MT)
+__device__ inline uint32_t mv_slot_table(const MvSlots& S, uint32_t M, uint32_t& SZ) {
+  const uint32_t w = S.sfk[M ? (uint32_t)__builtin_ctz(M) : 0u];
+  SZ = (w >> 8) & 0xFFu;
+  return w >> 16;
+}
+
+template <int ASZP, bool EG = true, bool PF = false, bool MT = false>
 __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, const MvSlots& S, uint32_t (&row)[ASZP],
                                        uint32_t (&acc)[ASZP], uint32_t& u) {
   constexpr int TQ = (mv_orw<ASZP>() - ASZP) / 4;
@@ -213,8 +236,10 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
   const uint32_t k = ent.x >> 24, M = ent.y;
   if (GS_OOB(u, a.N, a.err, "multi frontier node")) u = 0;
   const uint32_t nq = (a.Sg + 3) >> 2;
+  uint32_t tsz = 0, tb = 0;  // (MT) the entry's table and its ring size
+  if constexpr (MT) tb = mv_slot_table(S, M, tsz);
   // the row (with its failure classes) and every slot quad's masks: independent loads
-  const uint32_t* orow = a.own + (size_t)u * a.ORW;
+  const uint32_t* orow = (MT ? a.own + tb * a.own_ts : a.own) + (size_t)u * a.ORW;
   load_row<ASZP>(orow, row);
   uint32_t tail[4 * TQ];
   {
@@ -236,8 +261,8 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
     for (int s = 0; s < ASZP; ++s) fc[s] = (tail[1 + s / 4] >> (8 * (s % 4))) & 0xFFu;
   } else {  // an origin of lower bucket: entry min(bucket[u], bucket[origin])
     const uint32_t ent_i = u * NB + k;
-    hv = a.hl[ent_i];
-    load_row<ASZP>(a.peers + (size_t)ent_i * ASZP, row);
+    hv = (MT ? a.hl + tb * a.t_ents : a.hl)[ent_i];
+    load_row<ASZP>((MT ? a.peers + tb * a.t_rows : a.peers) + (size_t)ent_i * ASZP, row);
 #pragma unroll
     for (int s = 0; s < ASZP; ++s) fc[s] = a.any_fail ? a.fcls[row[s]] : 0xFFu;
   }
@@ -251,7 +276,7 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
               ((uint32_t)(m4[q].w == 0) << 3)) << (4 * q);
     plain = M & S.pz & pmz;
     if (plain) {
-      const uint32_t SZ = a.ASZ, full = (1u << SZ) - 1u;
+      const uint32_t SZ = MT ? tsz : a.ASZ, full = (1u << SZ) - 1u;
       const uint32_t L = min(len, SZ), nf = min(L, a.fanout);
       const uint32_t pre = (1u << nf) - 1u, nxp = L > a.fanout ? 1u << a.fanout : 0u;  // ring positions
       const uint32_t tkn = ((pre << head) | (pre >> (SZ - head))) & full;               // physical slots
@@ -326,8 +351,8 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
         continue;
       }
       const uint32_t pm = t == 0 ? m4[q].x : t == 1 ? m4[q].y : t == 2 ? m4[q].z : m4[q].w;
-      const uint32_t f = S.sfk[j];
-      uint32_t tk = taken_slots<ASZP>(row, head, len, a.ASZ, pm, S.sorg[j], PF ? S.sfan[j] : a.fanout);
+      const uint32_t f = MT ? S.sfk[j] & 0xFFu : S.sfk[j];
+      uint32_t tk = taken_slots<ASZP>(row, head, len, MT ? tsz : a.ASZ, pm, S.sorg[j], PF ? S.sfan[j] : a.fanout);
       if (f) {  // failed peers burn their fanout slot (gossip.rs:538-541)
 #pragma unroll
         for (int s = 0; s < ASZP; ++s)
@@ -351,9 +376,21 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
 // Node v's new slots as frontier entries, one per distinct entry k: slots whose origin
 // bucket is >= bucket[v] share v's own entry, the rest split by origin bucket. Returns
 // the entry count; writes them at out[pos..] when out != nullptr.
-template <class Put>
-__device__ inline uint32_t mv_parts_to(const uint32_t* gt, uint32_t v, uint32_t nw, uint32_t bv, Put put) {
+// MT (several trajectory tables; gtt: the group's table words in global memory, a.gt): the new
+// slots are split by table first -- an entry's slots share one table -- and each table's share
+// by entry k as above: at most min(Sg, 28) entries per node and level.
+template <bool MT = false, class Put>
+__device__ inline uint32_t mv_parts_to(const uint32_t* gt, uint32_t v, uint32_t nw, uint32_t bv, Put put,
+                                       const uint32_t* gtt = nullptr) {
   uint32_t n = 0;
+  if constexpr (MT) {
+    const uint32_t nt = gtt[GT_NT];
+    for (uint32_t i = 0; i < nt; ++i) {
+      const uint32_t nwt = nw & gtt[GT_TM + i];
+      if (nwt) n += mv_parts_to<false>(gt, v, nwt, bv, [&](uint32_t k, uint2 x) { put(n + k, x); });
+    }
+    return n;
+  }
   const uint32_t own = nw & gt[GT_OWN + bv];
   if (own) put(n++, make_uint2(v | (bv << 24), own));
   const uint32_t rest = nw & ~own;
@@ -367,11 +404,12 @@ __device__ inline uint32_t mv_parts_to(const uint32_t* gt, uint32_t v, uint32_t 
   return n;
 }
 
+template <bool MT = false>
 __device__ inline uint32_t mv_parts(const uint32_t* gt, uint32_t v, uint32_t nw, uint32_t bv, uint2* out,
-                                    uint32_t pos) {
-  return mv_parts_to(gt, v, nw, bv, [&](uint32_t k, uint2 x) {
+                                    uint32_t pos, const uint32_t* gtt = nullptr) {
+  return mv_parts_to<MT>(gt, v, nw, bv, [&](uint32_t k, uint2 x) {
     if (out) out[pos + k] = x;
-  });
+  }, gtt);
 }
 
 template <class T>

@@ -224,6 +224,8 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
   if (traj) {
     prm.active_set_size = 0;  // the capacity: the largest table
     for (uint32_t t = 0; t < n_traj; ++t) prm.active_set_size = std::max(prm.active_set_size, traj[t].active_set_size);
+    // bfs_mode GS_BFS_MULTI names the multi-source table engine (any other mode behaves as before)
+    if (cfg->bfs_mode == GS_BFS_MULTI) prm.flags |= GS_FLAG_TRAJ_MULTI;
     r = gs_create_traj(&prm, stakes, n, n_sims, traj, n_traj, &e);
   } else {
     r = gs_create(&prm, stakes, n, n_sims, &e);

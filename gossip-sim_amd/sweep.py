@@ -26,11 +26,12 @@ trajectory: `fanout_groups` splits the sweep into the sims that share a size, an
 active-set trajectory tables (gs_create_traj), one per (size, probability) pair, so a
 rank's whole share of such a sweep runs as one engine (run_simulations(aszs=, rot_probs=))
 when the network fits the workgroup engine (`traj_supported`); otherwise the share runs as
-`run_sweep` does, one engine per value.
+`run_sweep` does, one engine per value -- or, with multi=True, as one multi-source table
+engine (bfs_mode GS_BFS_MULTI) at any node count that BFS supports (`traj_multi_supported`).
 """
 import numpy as np
 
-from . import run_simulations, traj_supported
+from . import GS_BFS_MULTI, run_simulations, traj_multi_supported, traj_supported
 
 F64_NAMES = ["coverage", "rmr", "branching", "hop_mean", "hop_median", "coverage_stats", "rmr_stats",
              "branching_stats", "aggregate_hops", "ldh", "stranded", "stranded_round_mean",
@@ -270,10 +271,8 @@ _PER_SIM = ("origin_ranks", "min_ingress", "thresholds", "fractions")  # (one va
 _PER_TABLE = ("fanout", "asz", "p", "n_sims") + _PER_SIM
 
 
-def traj_batchable(cfgs, n_nodes):
-    """Can these run_simulations kwargs (one single-sim dict per value) run as one engine: they
-    may differ only in asz / p / fanout (and the per-sim lists), and the network must fit the
-    workgroup engine at their largest fanout and size."""
+def _traj_mergeable(cfgs):
+    """The kwargs (one single-sim dict per value) differ only in asz / p / fanout and the per-sim lists."""
     if not cfgs:
         return False
     rest = [{k: v for k, v in c.items() if k not in _PER_TABLE} for c in cfgs]
@@ -282,21 +281,45 @@ def traj_batchable(cfgs, n_nodes):
     for k in _PER_SIM:
         if len({c.get(k) is None for c in cfgs}) > 1:
             return False
+    return True
+
+
+def traj_batchable(cfgs, n_nodes):
+    """Can these run_simulations kwargs (one single-sim dict per value) run as one engine: they
+    may differ only in asz / p / fanout (and the per-sim lists), and the network must fit the
+    workgroup engine at their largest fanout and size."""
+    if not _traj_mergeable(cfgs):
+        return False
     return traj_supported(n_nodes, max(c.get("fanout", 6) for c in cfgs), max(c.get("asz", 12) for c in cfgs))[0]
 
 
-def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_device=None, runner=None):
+def traj_batchable_multi(cfgs, n_nodes):
+    """traj_batchable for the multi-source table engine (bfs_mode GS_BFS_MULTI): the same rule on
+    the kwargs, and the network must pass traj_multi_supported with one slot per value at their
+    largest fanout and size -- any node count the multi-source BFS supports."""
+    if not _traj_mergeable(cfgs):
+        return False
+    return traj_multi_supported(n_nodes, len(cfgs), max(c.get("fanout", 6) for c in cfgs),
+                                max(c.get("asz", 12) for c in cfgs))
+
+
+def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_device=None, runner=None, multi=False):
     """run_sweep with each rank's share as ONE engine of several trajectory tables: the same
     arguments (values dealt round-robin over the ranks, make_cfg(value) -> kwargs of
     run_simulations) and bit-identical results. A share that cannot batch (traj_batchable)
-    runs one engine per value, as run_sweep does."""
+    runs one engine per value, as run_sweep does -- unless multi=True and it passes
+    traj_batchable_multi: then it runs as ONE multi-source table engine (bfs_mode GS_BFS_MULTI)."""
     tdist, rank, world = _dist_info(group)
     runner = runner or run_simulations
     local = {}
     mine = shard(len(values), rank, world)
     cfgs = [dict(make_cfg(values[i])) for i in mine]
-    if len(mine) > 1 and traj_batchable(cfgs, len(stakes)):
+    batch = len(mine) > 1 and traj_batchable(cfgs, len(stakes))
+    as_multi = multi and len(mine) > 1 and not batch and traj_batchable_multi(cfgs, len(stakes))
+    if batch or as_multi:
         kw = {k: v for k, v in cfgs[0].items() if k not in _PER_TABLE}
+        if as_multi:
+            kw["bfs_mode"] = GS_BFS_MULTI
         for k in _PER_SIM:
             if cfgs[0].get(k) is not None:
                 kw[k] = [x for c in cfgs for x in c[k]]

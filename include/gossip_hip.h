@@ -26,7 +26,9 @@
  *    batches like the others (its sims with the same active-set size, see sweep.py).
  *    An engine made by gs_create_traj holds several trajectories (tables), each with its
  *    own active-set size and rotation probability and its own range of slots, so the
- *    sims of an active-set-size or rotate-probability sweep batch as well.
+ *    sims of an active-set-size or rotate-probability sweep batch as well: on the
+ *    workgroup engine, and with GS_FLAG_TRAJ_MULTI on the multi-source BFS at any node
+ *    count that BFS supports (gs_traj_multi_supported).
  *  - The engine owns all device memory. Inputs are copied at call time; outputs
  *    go to caller buffers with explicit capacities (too small => GS_ERANGE).
  *  - An engine is not re-entrant; use one engine per device per host thread.
@@ -78,7 +80,7 @@ enum { GS_BFS_AUTO = 0, GS_BFS_WORKGROUP = 1, GS_BFS_LEVEL = 2, GS_BFS_BINNED = 
        GS_BFS_HYBRID = 5 };
 enum { GS_FLAG_PROFILE = 1, GS_FLAG_SPLIT_ROUND = 2, GS_FLAG_NARROW_WAVE_PATH = 4, GS_FLAG_BINNED_ALL_LEVELS = 8,
        GS_FLAG_WIDE_RECORDS = 16, GS_FLAG_NO_SMALL_LEVELS = 32, GS_FLAG_MISPREDICT_LEVELS = 64,
-       GS_FLAG_FRONTIER_EXCHANGE = 128 };
+       GS_FLAG_FRONTIER_EXCHANGE = 128, GS_FLAG_TRAJ_MULTI = 256 };
 
 typedef struct gs_params {
   uint32_t push_fanout;         /* Config::gossip_push_fanout (gossip.rs:113) */
@@ -109,7 +111,10 @@ typedef struct gs_params {
                                    (same results; a test of the misprediction path);
                                    GS_FLAG_FRONTIER_EXCHANGE: gs_create_part makes a frontier-exchange
                                    rank (gs_part_xbfs_*: it expands only its own frontier and
-                                   exchanges each level's push records with their owners) */
+                                   exchanges each level's push records with their owners);
+                                   GS_FLAG_TRAJ_MULTI: gs_create_traj may build its tables on the
+                                   multi-source BFS (GS_BFS_MULTI, or AUTO beyond the workgroup
+                                   engine); no effect on any other call */
 } gs_params;
 
 typedef struct gs_slot {
@@ -157,7 +162,16 @@ int gs_create(const gs_params* params, const uint64_t* stakes, uint32_t n_nodes,
  * and probability. Everything addressed by slot reads the slot's own table; the calls that
  * name an entry take the table (the _traj forms below; on an engine with several tables the
  * un-suffixed ones return GS_EINVAL). No reference interface: the reference builds one
- * Cluster per value (gossip_main.rs:775-797, 925-951). */
+ * Cluster per value (gossip_main.rs:775-797, 925-951).
+ * With GS_FLAG_TRAJ_MULTI in params.flags the tables may also live on the multi-source BFS:
+ * bfs_mode GS_BFS_MULTI builds a multi-source table engine at any size that BFS supports
+ * (gs_traj_multi_supported: host arithmetic only, returns 1 / 0 for a network of n_nodes, an
+ * engine of n_slots, a push-fanout capacity and a largest active-set size), GS_BFS_AUTO picks
+ * WORKGROUP when gs_traj_supported and else MULTI, and LEVEL / BINNED / HYBRID stay GS_EINVAL.
+ * Slot groups stay consecutive runs of slots, independent of the tables; a frontier entry
+ * belongs to one table; the persistent and the launched level loop both run such engines, and
+ * every slot stays bit-identical to its own per-value engine. Without the flag nothing
+ * changes. */
 typedef struct gs_traj {
   uint32_t active_set_size;      /* 1..params.active_set_size */
   double rotation_probability;   /* [0,1] */
@@ -167,6 +181,7 @@ int gs_create_traj(const gs_params* params, const uint64_t* stakes, uint32_t n_n
                    const gs_traj* traj, uint32_t n_traj, gs_engine** out);
 int gs_engine_traj(gs_engine* e, gs_traj* out, uint32_t cap, uint32_t* n_traj); /* reads the tables back */
 int gs_traj_supported(uint32_t n_nodes, uint32_t push_fanout, uint32_t max_active_set_size, int* fused);
+int gs_traj_multi_supported(uint32_t n_nodes, uint32_t n_slots, uint32_t push_fanout, uint32_t max_active_set_size);
 void gs_destroy(gs_engine* e);
 const char* gs_last_error(void);
 /* sha256 prefix (16 hex digits) of the device sources this library was built from; the
@@ -389,7 +404,9 @@ int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes,
  * rotate-probability sweep as one engine): one value per sim, or NULL for cfg's. The sims are
  * grouped by (size, probability) into the tables of one gs_create_traj engine -- equal pairs
  * need not be adjacent -- and the results come back in sim order. Both NULL is exactly
- * gs_run_simulations_fanouts; one distinct pair is that call at the pair's values. */
+ * gs_run_simulations_fanouts; one distinct pair is that call at the pair's values. With
+ * cfg->bfs_mode == GS_BFS_MULTI and several pairs the call sets GS_FLAG_TRAJ_MULTI itself and
+ * the engine is a multi-source table engine; any other mode behaves as gs_create_traj does. */
 int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_sims,
                             const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                             const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,

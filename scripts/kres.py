@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel resources from hipcc -Rpass-analysis=kernel-resource-usage (stdin): name,
-VGPRs, scratch bytes per lane, waves per SIMD, SGPR/VGPR spills. usage:
+VGPRs, scratch bytes per lane, static LDS bytes per block, waves per SIMD, SGPR/VGPR spills. usage:
 hipcc ... -Rpass-analysis=kernel-resource-usage 2>&1 | python3 scripts/kres.py [name-filter]"""
 import re
 import subprocess
@@ -17,6 +17,7 @@ for line in sys.stdin:
     if cur is None:
         continue
     for key, pat in (("vgpr", r"\sVGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+                     ("lds", r"LDS Size \[bytes/block\]: (\d+)"),
                      ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"),
                      ("vspill", r"VGPRs Spill: (\d+)")):
         m = re.search(pat, line)
@@ -27,5 +28,6 @@ dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, t
 for r, d in zip(rows, dem):
     if filt and filt not in d:
         continue
-    print(f"{d[:70]:70s} vgpr {r.get('vgpr', '?'):>4} scratch {r.get('scratch', '?'):>4} occ {r.get('occ', '?'):>2} "
+    print(f"{d[:70]:70s} vgpr {r.get('vgpr', '?'):>4} scratch {r.get('scratch', '?'):>4} lds {r.get('lds', '?'):>6} "
+          f"occ {r.get('occ', '?'):>2} "
           f"sspill {r.get('sspill', '?'):>3} vspill {r.get('vspill', '?'):>3}")
