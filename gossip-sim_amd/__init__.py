@@ -111,6 +111,9 @@ EXPORTS = {
     "gs_create_traj": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                  C.POINTER(C.c_void_p)]),
     "gs_engine_traj": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "gs_create_traj_seeds": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gs_engine_traj_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "gs_traj_supported": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
     "gs_traj_multi_supported": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "gs_set_active_set_entry_traj": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -121,6 +124,9 @@ EXPORTS = {
     "gs_run_simulations_traj": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_void_p)]),
+    "gs_run_simulations_seeds": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_void_p)]),
     "gs_destroy": (None, [C.c_void_p]),
     "gs_set_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "gs_set_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -275,7 +281,10 @@ class Engine:
     table t serves the next n_slots slots (their counts sum to the engine's), the capacity is
     the largest size, and `active_set_size` / `rotation_probability` are unused. traj_multi=True
     (GS_FLAG_TRAJ_MULTI) lets the tables live on the multi-source BFS: bfs_mode=GS_BFS_MULTI at
-    any size it supports, AUTO beyond the workgroup engine."""
+    any size it supports, AUTO beyond the workgroup engine. Tuples of four, (active_set_size,
+    rotation_probability, n_slots, seed), give every table its own Philox key (gs_create_traj_seeds;
+    `seed` is then unused): a slot of such a table equals an Engine(seed=that seed) at its size and
+    probability. If any tuple carries a seed, all must."""
 
     def __init__(self, stakes, n_slots, *, fanout=6, active_set_size=12, rotation_probability=0.013333, seed=0,
                  device=0, bfs_mode=GS_BFS_AUTO, inbound_capacity=0, profile=False, split_round=False,
@@ -285,7 +294,14 @@ class Engine:
         if trajectories is not None:
             if part is not None:
                 raise ValueError("Engine: partition ranks take no trajectory tables")
-            trajectories = [(int(a), float(q), int(k)) for a, q, k in trajectories]
+            trajectories = [tuple(t) for t in trajectories]
+            if len({len(t) for t in trajectories}) > 1 or any(len(t) not in (3, 4) for t in trajectories):
+                raise ValueError("Engine: trajectories are (active_set_size, rotation_probability, n_slots) or, for "
+                                 "every table, (active_set_size, rotation_probability, n_slots, seed)")
+            tseeds = None
+            if trajectories and len(trajectories[0]) == 4:
+                tseeds = np.array([int(t[3]) for t in trajectories], dtype=np.uint64)
+            trajectories = [(int(t[0]), float(t[1]), int(t[2])) for t in trajectories]
             active_set_size = max([a for a, _, _ in trajectories], default=active_set_size)
         self.stakes = np.ascontiguousarray(stakes, dtype=np.uint64)
         self.n = len(self.stakes)
@@ -302,8 +318,12 @@ class Engine:
         h = C.c_void_p()
         if trajectories is not None:
             arr = (Traj * max(1, len(trajectories)))(*[Traj(a, q, k) for a, q, k in trajectories])
-            _check(L.gs_create_traj(C.byref(p), _ptr(self.stakes), self.n, n_slots, C.cast(arr, C.c_void_p),
-                                    len(trajectories), C.byref(h)))
+            if tseeds is not None:
+                _check(L.gs_create_traj_seeds(C.byref(p), _ptr(self.stakes), self.n, n_slots, C.cast(arr, C.c_void_p),
+                                              len(trajectories), _ptr(tseeds), C.byref(h)))
+            else:
+                _check(L.gs_create_traj(C.byref(p), _ptr(self.stakes), self.n, n_slots, C.cast(arr, C.c_void_p),
+                                        len(trajectories), C.byref(h)))
         elif part is None:
             _check(L.gs_create(C.byref(p), _ptr(self.stakes), self.n, n_slots, C.byref(h)))
         else:  # (rank, nranks): one rank of a node-range partition (gossip_sim_amd.partition)
@@ -368,6 +388,14 @@ class Engine:
         arr = (Traj * 256)()
         _check(lib().gs_engine_traj(self.h, C.cast(arr, C.c_void_p), 256, C.byref(n)))
         return [(arr[t].active_set_size, arr[t].rotation_probability, arr[t].n_slots) for t in range(n.value)]
+
+    def table_seeds(self):
+        """The Philox key of each table (the engine's seed for every table of an engine made
+        without per-table seeds)."""
+        n = C.c_uint32()
+        out = np.zeros(max(1, self.n_slots), dtype=np.uint64)
+        _check(lib().gs_engine_traj_seeds(self.h, _ptr(out), len(out), C.byref(n)))
+        return [int(x) for x in out[:n.value]]
 
     def set_entry(self, node, bucket, peers, table=None):
         a = np.ascontiguousarray(peers, dtype=np.uint32)
@@ -592,11 +620,14 @@ class SimResult:
 def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, thresholds=None, fractions=None,
                     fanout=6, asz=12, iterations=1, warm_up=200, p=0.013333, thr=0.15, min_ingress_nodes=2,
                     fraction_to_fail=0.1, when_to_fail=0, nb_stranded=10, nb_message=5, nb_hops=15, test_type=0,
-                    seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None, aszs=None, rot_probs=None):
+                    seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None, aszs=None, rot_probs=None, seeds=None):
     """gossip_main.rs run_simulation for n_sims sims as slots of one engine.
     fanouts: a push fanout per sim (the engine's capacity is their maximum; `fanout` is unused then).
     aszs / rot_probs: an active-set size / rotation probability per sim (default `asz` / `p`); sims
-    with equal pairs share a trajectory table of one engine, and results stay in sim order."""
+    with equal pairs share a trajectory table of one engine, and results stay in sim order.
+    seeds: a Philox seed per sim (`seed` is unused then): the tables are the distinct (size,
+    probability, seed) triples, so seed replicas run as one engine, each sim equal to its own
+    run_simulations(seed=...) call."""
     st = np.ascontiguousarray(stakes, dtype=np.uint64)
     cfg = SimConfig(fanout, asz, iterations, warm_up, min_ingress_nodes, when_to_fail, p, thr, fraction_to_fail,
                     nb_stranded, nb_message, nb_hops, test_type, seed, device, bfs_mode)
@@ -613,8 +644,17 @@ def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, th
     for name, x in (("aszs", az), ("rot_probs", rp)):
         if x is not None and x.shape != (n_sims,):
             raise ValueError(f"run_simulations: {name} needs exactly n_sims = {n_sims} values")
+    sd = arr(seeds, np.uint64)
+    if sd is not None and sd.shape != (n_sims,):
+        raise ValueError(f"run_simulations: seeds needs exactly n_sims = {n_sims} values")
     h = C.c_void_p()
-    if az is None and rp is None:
+    if sd is not None:
+        _check(lib().gs_run_simulations_seeds(C.byref(cfg), _ptr(st), len(st), n_sims,
+                                              None if r is None else _ptr(r), None if mi is None else _ptr(mi),
+                                              None if th is None else _ptr(th), None if fr is None else _ptr(fr),
+                                              None if fo is None else _ptr(fo), None if az is None else _ptr(az),
+                                              None if rp is None else _ptr(rp), _ptr(sd), C.byref(h)))
+    elif az is None and rp is None:
         _check(lib().gs_run_simulations_fanouts(C.byref(cfg), _ptr(st), len(st), n_sims,
                                                 None if r is None else _ptr(r), None if mi is None else _ptr(mi),
                                                 None if th is None else _ptr(th), None if fr is None else _ptr(fr),

@@ -8,7 +8,10 @@
 // value of the engine; the reference raises a sim's set size to its fanout, which splits the
 // sweep into one engine per size). The test types that change the trajectory itself
 // (active-set-size, rotate-probability) give each value its own engine. --engine-plan FILE
-// writes the engines of a run. With --gpus K the simulations are dealt over K devices,
+// writes the engines of a run. --trials K repeats every simulation at the seeds --seed ..
+// --seed + K - 1 (value-major, trial-minor; each repeat is a simulation of its own): one engine per
+// (trajectory value, seed), or with --batch-sweeps one engine per device whose tables carry their
+// own seeds. With --gpus K the simulations are dealt over K devices,
 // one host thread and engine per device (results do not depend on the split: the
 // Philox contract makes every slot a pure function of its own parameters).
 //
@@ -76,6 +79,7 @@ struct Cli {
   std::string influx_file;  // offline Influx line protocol (gs_influx.cpp)
   uint64_t influx_time_base = 0;
   bool batch_sweeps = false;  // an active-set-size / rotate-probability / push-fanout sweep as one engine per device
+  uint64_t trials = 1;        // every simulation repeated at seeds seed .. seed + trials - 1
 };
 
 void usage() {
@@ -103,6 +107,10 @@ void usage() {
       "                       Networks beyond the workgroup engine (about 16,000 nodes) fall back to one engine\n"
       "                       per value, unless --bfs-mode 4 is given: then the tables live on the multi-source\n"
       "                       BFS at any node count it supports (one engine per device)\n"
+      "  --trials K [1]       repeat every simulation at the seeds --seed, --seed + 1, .. --seed + K - 1 (value-major,\n"
+      "                       trial-minor; each repeat is its own simulation in the report and in --save-results):\n"
+      "                       one engine per (trajectory value, seed), or with --batch-sweeps one engine per device\n"
+      "                       (a table per value and seed) under the same network limits; plan lines gain `seeds`\n"
       "  --influx-file PATH   write the Influx series (influx_db.rs) as line protocol to PATH\n"
       "  --influx-time-base NS  reproducible Influx timestamps NS + 1000 k (default: wall clock)\n"
       "gossip-sim write-accounts --account-file PATH --synthetic N [--num-nodes K] [--zero-stakes] [-f]");
@@ -177,6 +185,7 @@ Cli parse(int argc, char** argv) {
     else if (a == "--influx-file") c.influx_file = need(i);
     else if (a == "--influx-time-base") u64(i, c.influx_time_base);
     else if (a == "--batch-sweeps") c.batch_sweeps = true;
+    else if (a == "--trials") u64(i, c.trials);
     else die(2, "unexpected argument '" + a + "' (see --help)");
   }
   return c;
@@ -225,6 +234,7 @@ struct Job {
   bool traj = false;              // --batch-sweeps: an active-set table per (size, probability) of `aszs` / `probs`
   std::vector<uint32_t> aszs;     // per simulation
   std::vector<double> probs;
+  std::vector<uint64_t> seeds;    // --trials K > 1: per simulation (a table per size, probability and seed), else empty
 };
 
 void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsrep::SimArrays>& out,
@@ -233,7 +243,11 @@ void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsre
   cfg.device = j.device;
   gs_sim_result* r = nullptr;
   const int rc =
-      j.traj ? gs_run_simulations_traj(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+      j.traj && !j.seeds.empty()
+          ? gs_run_simulations_seeds(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+                                     j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(), j.fanouts.data(),
+                                     j.aszs.data(), j.probs.data(), j.seeds.data(), &r)
+      : j.traj ? gs_run_simulations_traj(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
                                        j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(), j.fanouts.data(),
                                        j.aszs.data(), j.probs.data(), &r)
              : gs_run_simulations_fanouts(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
@@ -325,6 +339,8 @@ int main(int argc, char** argv) {
   }
   if (c.influx != "n") die(1, "influx reporting over HTTP is not available offline (--influx n)");
   if (c.gpus < 1) die(2, "--gpus must be >= 1");
+  if (c.trials < 1) die(2, "--trials must be >= 1");
+  const uint64_t K = c.trials;
 
   if (c.origin_ranks.size() < num_sims) {
     gsrep::log_warn(stderr, TMAIN, "ERROR: not enough origin ranks provided for num_simulations! origin_ranks.len(): " +
@@ -407,13 +423,14 @@ int main(int argc, char** argv) {
     const bool per_value_engine = test_type == gsrep::ACTIVE_SET_SIZE || test_type == gsrep::ROTATE_PROBABILITY;
     // --batch-sweeps: the sweeps whose value changes the trajectory (and a push-fanout sweep's
     // sims of raised size) as tables of one engine, when the network fits the workgroup engine
-    bool traj = c.batch_sweeps && (per_value_engine || test_type == gsrep::PUSH_FANOUT);
+    // (--trials: the seeds are tables too, so every test type batches)
+    bool traj = c.batch_sweeps && (per_value_engine || test_type == gsrep::PUSH_FANOUT || K > 1);
     if (traj) {
       uint64_t fmax = 1, amax = 1;
       for (const auto& q : params) { fmax = std::max(fmax, q.gossip_push_fanout); amax = std::max(amax, q.gossip_active_set_size); }
       if (c.bfs_mode == GS_BFS_MULTI) {  // the tables on the multi-source BFS: any node count it supports
         if (amax > GS_MAX_ACTIVE_SET_SIZE ||
-            !gs_traj_multi_supported((uint32_t)stakes.size(), (uint32_t)std::min<uint64_t>(num_sims, 0xFFFFFFFFu),
+            !gs_traj_multi_supported((uint32_t)stakes.size(), (uint32_t)std::min<uint64_t>(num_sims * K, 0xFFFFFFFFu),
                                      (uint32_t)std::min<uint64_t>(fmax, 0xFFFFFFFFu), (uint32_t)amax)) {
           gsrep::log_info(stderr, TMAIN, "--batch-sweeps: " + std::to_string(stakes.size()) + " nodes at active-set size " +
                                              std::to_string(amax) + " do not fit the multi-source table engine; planning one engine per value");
@@ -453,14 +470,36 @@ int main(int argc, char** argv) {
       for (size_t d = 0; d < K; ++d)
         groups.emplace_back(b.begin() + b.size() * d / K, b.begin() + b.size() * (d + 1) / K);
     }
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
+    // --trials K > 1: unit i * K + k is simulation i at seed + k. Batched, the units of every
+    // value are one batch (split over the devices as above); else today's plan once per seed.
+    struct Unit { std::vector<size_t> sims; uint64_t k; };  // k: the trial (batched: unused)
+    std::vector<Unit> units;
+    if (K == 1) {
+      for (const auto& g : groups) units.push_back(Unit{g, 0});
+    } else if (traj) {
+      const size_t U = num_sims * K, D = std::min<size_t>(c.gpus, U);
+      for (size_t d = 0; d < D; ++d) {
+        Unit u{{}, 0};
+        for (size_t x = U * d / D; x < U * (d + 1) / D; ++x) u.sims.push_back(x);
+        units.push_back(std::move(u));
+      }
+    } else {
+      for (const auto& g : groups)
+        for (uint64_t k = 0; k < K; ++k) units.push_back(Unit{g, k});
+    }
+    for (size_t gi = 0; gi < units.size(); ++gi) {
       Job j;
-      j.cfg = base_cfg(params[groups[gi][0]]);
+      const bool by_unit = K > 1 && traj;  // the job's sims are unit indices
+      std::vector<size_t> vals;            // the simulation (value) of each of the job's sims
+      for (size_t x : units[gi].sims) vals.push_back(by_unit ? x / K : x);
+      j.cfg = base_cfg(params[vals[0]]);
       j.device = (int)(gi % c.gpus);
-      j.sims = groups[gi];
+      if (K == 1) j.sims = units[gi].sims;
+      else if (by_unit) { j.sims = units[gi].sims; for (size_t x : j.sims) j.seeds.push_back(c.seed + x % K); }
+      else { for (size_t i : vals) j.sims.push_back(i * K + units[gi].k); j.cfg.seed = c.seed + units[gi].k; }
       j.slot_fanouts = test_type == gsrep::PUSH_FANOUT;
       j.traj = traj;
-      for (size_t i : groups[gi]) {
+      for (size_t i : vals) {
         j.aszs.push_back((uint32_t)params[i].gossip_active_set_size);
         j.probs.push_back(std::min(params[i].probability_of_rotation, 1.0));
         j.ranks.push_back((uint32_t)params[i].origin_rank);
@@ -491,11 +530,23 @@ int main(int argc, char** argv) {
         std::fprintf(f, " rotation-probability ");
         for (size_t k = 0; k < j.probs.size(); ++k) std::fprintf(f, "%s%.17g", k ? "," : "", j.probs[k]);
       }
+      if (K > 1) {  // (only then: without --trials the lines stay as they were)
+        std::fprintf(f, " seeds ");
+        if (j.seeds.empty()) std::fprintf(f, "%" PRIu64, j.cfg.seed);
+        for (size_t k = 0; k < j.seeds.size(); ++k) std::fprintf(f, "%s%" PRIu64, k ? "," : "", j.seeds[k]);
+      }
       std::fprintf(f, "\n");
     }
     std::fclose(f);
   }
 
+  if (K > 1) {  // every repeat is a simulation of its own from here on (value-major, trial-minor)
+    std::vector<gsrep::SimParams> rep;
+    for (uint64_t i = 0; i < num_sims; ++i)
+      for (uint64_t k = 0; k < K; ++k) rep.push_back(params[i]);
+    params = std::move(rep);
+    num_sims *= K;
+  }
   std::vector<gsrep::SimArrays> sims(num_sims);
   if (!c.replay_results.empty()) {
     std::string err;

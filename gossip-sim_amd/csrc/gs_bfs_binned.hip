@@ -792,7 +792,8 @@ hipError_t launch_own_rows(Engine& e, const uint32_t* list, const uint32_t* coun
     GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_own_rows<A>, dim3(grid), dim3(256), 0, e.st, e.bucket,
                                                 e.peers + t * e.t_rows, e.hl + t * e.t_ents,
                                                 list ? list + (size_t)t * e.N : nullptr, count ? count + 2 * t : nullptr,
-                                                e.N, e.ORW, e.mv_fcls, e.own + t * e.own_ts));
+                                                e.N, e.ORW, e.mv_fcls ? e.mv_fcls + t * e.t_frank : nullptr,
+                                                e.own + t * e.own_ts));
   return hipGetLastError();
 }
 

@@ -1119,8 +1119,10 @@ hipError_t mv_update_failures(Engine& e, const std::vector<uint32_t>& nf) {
   if ((r = hipMemcpyAsync(e.mv_fk, fk.data(), e.S, hipMemcpyHostToDevice, e.st))) return r;
   if (!T.empty()) {
     if ((r = hipMemcpyAsync(e.mv_thr, T.data(), T.size() * 4, hipMemcpyHostToDevice, e.st))) return r;
-    hipLaunchKernelGGL(k_mv_fcls, dim3(std::min<uint32_t>((e.N + 255) / 256, 4096)), dim3(256), 0, e.st, e.frank,
-                       e.mv_thr, (uint32_t)T.size(), e.N, e.mv_fcls);
+    // (the counts T stay engine-wide; each table's classes come from its own ranks when the keys differ)
+    for (uint32_t t = 0; t < (e.t_frank ? e.T : 1u); ++t)
+      hipLaunchKernelGGL(k_mv_fcls, dim3(std::min<uint32_t>((e.N + 255) / 256, 4096)), dim3(256), 0, e.st,
+                         e.frank + t * e.t_frank, e.mv_thr, (uint32_t)T.size(), e.N, e.mv_fcls + t * e.t_frank);
     if ((r = launch_own_rows(e, nullptr, nullptr))) return r;  // the rows carry their peers' failure classes
   }
   return hipStreamSynchronize(e.st);  // fk and T are host temporaries
@@ -1137,6 +1139,7 @@ MvArgs mv_args(Engine& e, const MvGroup& gr, uint32_t g) {
   // several trajectory tables: the MT kernels, which read every slot's fanout (the table
   // engine keeps e.sfan from create on)
   a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents; a.own_ts = e.own_ts;
+  a.t_fcls = e.t_frank;
   if (a.stab) a.sfan = e.sfan;
   a.pool = e.mv_pool; a.pused = e.mv_pused;
   a.N = e.N; a.SP = e.SP; a.ASZ = e.ASZ; a.fanout = e.fanout; a.capin = e.capin; a.s0 = gr.s0; a.Sg = gr.sg;

@@ -199,7 +199,7 @@ __device__ inline void pb_expand_wide(const MvArgs& a, uint2 ent, bool valid, co
     hv = (MT ? a.hl + tb * a.t_ents : a.hl)[ent_i];
     load_row<ASZP>((MT ? a.peers + tb * a.t_rows : a.peers) + (size_t)ent_i * ASZP, rw);
 #pragma unroll
-    for (int s = 0; s < ASZP; ++s) fc[s] = a.any_fail ? a.fcls[rw[s]] : 0xFFu;
+    for (int s = 0; s < ASZP; ++s) fc[s] = a.any_fail ? (MT ? a.fcls + tb * a.t_fcls : a.fcls)[rw[s]] : 0xFFu;
   }
   uint32_t tk = 0;
   if (inM) {

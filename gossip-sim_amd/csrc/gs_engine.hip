@@ -221,9 +221,11 @@ static size_t part_record_cap(size_t N, size_t S, uint32_t K) {
 // K == 0: an engine over all nodes; K >= 1: rank `rank` of a node-range partition over K
 // ranks (K == 1: one rank owning every node, the exchange calls still available).
 // traj != null (gs_create_traj, n_traj >= 2 here): the engine's trajectory tables; prm's
-// active_set_size is then the capacity and its rotation probability is unused.
+// active_set_size is then the capacity and its rotation probability is unused. seeds != null
+// (gs_create_traj_seeds, the keys differ): table t's Philox key; prm's seed is then unused.
 static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots, uint32_t rank,
-                         uint32_t K, gs_engine** out, const gs_traj* traj = nullptr, uint32_t n_traj = 0) {
+                         uint32_t K, gs_engine** out, const gs_traj* traj = nullptr, uint32_t n_traj = 0,
+                         const uint64_t* seeds = nullptr) {
   const bool part = K >= 1;
   if (!part) K = 1;
   if (!prm || !stakes || !out) return fail(GS_EINVAL, "null argument");
@@ -265,6 +267,7 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
     for (uint32_t t = 0; t < n_traj; ++t) {
       TrajTab tt;
       tt.asz = traj[t].active_set_size; tt.p = traj[t].rotation_probability; tt.s0 = s0; tt.ns = traj[t].n_slots;
+      tt.seed = seeds ? seeds[t] : prm->seed;
       for (uint32_t o = 0; o < tt.ns; ++o) e->h_stab[s0 + o] = t;
       s0 += tt.ns;
       e->traj.push_back(tt);
@@ -272,7 +275,12 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   } else {
     TrajTab tt;
     tt.asz = e->ASZ; tt.p = prm->rotation_probability; tt.s0 = 0; tt.ns = n_slots;
+    tt.seed = prm->seed;
     e->traj.push_back(tt);
+  }
+  if (seeds) {  // keys that differ: fail ranks (and failure classes) per table
+    e->t_frank = n;
+    e->prm.seed = seeds[0];
   }
   if (hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking) != hipSuccess) {
     destroy_engine(e);
@@ -419,7 +427,7 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   ALLOC(e->hl, e->T * e->t_ents, 0);
   if (e->T > 1) {
     std::vector<TrajDev> td(e->T);
-    for (uint32_t t = 0; t < e->T; ++t) td[t] = TrajDev{e->traj[t].asz, e->traj[t].s0, e->traj[t].p};
+    for (uint32_t t = 0; t < e->T; ++t) td[t] = TrajDev{e->traj[t].asz, e->traj[t].s0, e->traj[t].p, e->traj[t].seed};
     ALLOC(e->stab, S, 0);
     ALLOC(e->ttab, e->T, 0);
     if (hipMemcpyAsync(e->stab, e->h_stab.data(), S * 4, hipMemcpyHostToDevice, e->st) != hipSuccess ||
@@ -429,7 +437,7 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
       return fail(GS_EHIP, "trajectory table upload");
     }
   }
-  ALLOC(e->frank, N, 0);
+  ALLOC(e->frank, e->t_frank ? e->T * N : N, 0);
   ALLOC(e->srank, N, 0);
   ALLOC(e->by_srank, N, 0);
   ALLOC(e->prank, N, 0);
@@ -539,7 +547,7 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
         e->pb_registered = true;
       }
     }
-    ALLOC(e->mv_fcls, N, 0xFF);
+    ALLOC(e->mv_fcls, e->t_frank ? e->T * N : N, 0xFF);
     ALLOC(e->mv_fk, S, 0);
     ALLOC(e->mv_thr, S, 0);
     ALLOC(e->mv_gtab, (size_t)((S + g.GW - 1) / g.GW) * GT_STRIDE, 0);
@@ -665,8 +673,10 @@ int gs_traj_multi_supported(uint32_t n_nodes, uint32_t n_slots, uint32_t push_fa
   return mv_supported(g, aszp) && area_ok ? 1 : 0;
 }
 
-int gs_create_traj(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots, const gs_traj* traj,
-                   uint32_t n_traj, gs_engine** out) {
+// seeds: gs_create_traj_seeds' keys when they differ (n_traj >= 2 then), else null: every table
+// draws on prm's seed
+static int create_traj(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots, const gs_traj* traj,
+                       uint32_t n_traj, const uint64_t* seeds, gs_engine** out) {
   if (!prm || !stakes || !out || !traj) return fail(GS_EINVAL, "null argument");
   *out = nullptr;
   if (n_traj == 0) return fail(GS_EINVAL, "gs_create_traj: n_traj must be >= 1");
@@ -705,7 +715,12 @@ int gs_create_traj(const gs_params* prm, const uint64_t* stakes, uint32_t n, uin
     return create_engine(&p, stakes, n, n_slots, 0, 0, out);
   }
   p.rotation_probability = 0.0;  // (unused: every table carries its own)
-  return create_engine(&p, stakes, n, n_slots, 0, 0, out, traj, n_traj);
+  return create_engine(&p, stakes, n, n_slots, 0, 0, out, traj, n_traj, seeds);
+}
+
+int gs_create_traj(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots, const gs_traj* traj,
+                   uint32_t n_traj, gs_engine** out) {
+  return create_traj(prm, stakes, n, n_slots, traj, n_traj, nullptr, out);
 }
 
 int gs_engine_traj(gs_engine* eh, gs_traj* out, uint32_t cap, uint32_t* n_traj) {
@@ -719,6 +734,30 @@ int gs_engine_traj(gs_engine* eh, gs_traj* out, uint32_t cap, uint32_t* n_traj) 
     out[t].rotation_probability = e->traj[t].p;
     out[t].n_slots = e->traj[t].ns;
   }
+  return GS_OK;
+}
+
+int gs_create_traj_seeds(const gs_params* prm, const uint64_t* stakes, uint32_t n, uint32_t n_slots,
+                         const gs_traj* traj, uint32_t n_traj, const uint64_t* seeds, gs_engine** out) {
+  if (!seeds) return gs_create_traj(prm, stakes, n, n_slots, traj, n_traj, out);
+  if (!prm || !stakes || !out || !traj) return fail(GS_EINVAL, "null argument");
+  *out = nullptr;
+  if (n_traj == 0) return fail(GS_EINVAL, "gs_create_traj: n_traj must be >= 1");
+  gs_params p = *prm;
+  p.seed = seeds[0];
+  bool equal = true;
+  for (uint32_t t = 1; t < n_traj; ++t) equal = equal && seeds[t] == seeds[0];
+  // equal keys: gs_create_traj's engine at that seed (one rank array, the same kernels and memory)
+  return create_traj(&p, stakes, n, n_slots, traj, n_traj, equal ? nullptr : seeds, out);
+}
+
+int gs_engine_traj_seeds(gs_engine* eh, uint64_t* out, uint32_t cap, uint32_t* n_traj) {
+  Engine* e = reinterpret_cast<Engine*>(eh);
+  if (!e || !n_traj) return fail(GS_EINVAL, "null argument");
+  *n_traj = e->T;
+  if (e->T > cap) return fail(GS_ERANGE, "seed buffer too small");
+  if (!out) return fail(GS_EINVAL, "null argument");
+  for (uint32_t t = 0; t < e->T; ++t) out[t] = e->traj[t].seed;
   return GS_OK;
 }
 
@@ -934,10 +973,12 @@ int gs_fail_nodes(gs_engine* eh, const double* fraction) {
     uint32_t *ids = nullptr, *sorted = nullptr;
     if (!sc.get(&keys, e->N * 8ull) || !sc.get(&ids, e->N * 4ull) || !sc.get(&sorted, e->N * 4ull))
       return fail(GS_ENOMEM, "fail_nodes scratch");
-    HIPC(launch_fail_keys(*e, keys, ids));
-    if (int s = sort_ids_by_key(*e, keys, sorted)) return s;
-    HIPC(launch_scatter_rank(*e, sorted, e->frank));
-    HIPC(hipStreamSynchronize(e->st));
+    for (uint32_t t = 0; t < (e->t_frank ? e->T : 1u); ++t) {  // every table's ranks on its own FAIL keys
+      HIPC(launch_fail_keys(*e, e->traj[t].seed, keys, ids));
+      if (int s = sort_ids_by_key(*e, keys, sorted)) return s;
+      HIPC(launch_scatter_rank(*e, sorted, e->frank + t * e->t_frank));
+      HIPC(hipStreamSynchronize(e->st));
+    }
     e->failed_ranked = true;
   }
   std::vector<uint32_t> nf(e->S);
@@ -1490,7 +1531,8 @@ int gs_read_failed(gs_engine* eh, uint32_t slot, uint8_t* failed) {
   SLOT_CHECK(slot);
   std::vector<uint32_t> fr(e->N);
   uint32_t nf = 0;
-  HIPC(hipMemcpyAsync(fr.data(), e->frank, e->N * 4ull, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipMemcpyAsync(fr.data(), e->frank + e->h_stab[slot] * e->t_frank, e->N * 4ull, hipMemcpyDeviceToHost,
+                      e->st));  // the slot's own table's ranks
   HIPC(hipMemcpyAsync(&nf, e->nfail + slot, 4, hipMemcpyDeviceToHost, e->st));
   HIPC(hipStreamSynchronize(e->st));
   for (uint32_t v = 0; v < e->N; ++v) failed[v] = nf && fr[v] < nf;

@@ -42,8 +42,9 @@ struct MvGeom {
 };
 // One active-set trajectory table (gs_create_traj): its own ring size and rotation probability,
 // serving the slots [s0, s0 + ns). The device copy (TrajDev) is what the round kernel reads.
-struct TrajTab { uint32_t asz = 0, s0 = 0, ns = 0; double p = 0; };
-struct TrajDev { uint32_t asz, s0; double p; };
+// seed: the table's Philox key (gs_create_traj_seeds; the engine's seed otherwise).
+struct TrajTab { uint32_t asz = 0, s0 = 0, ns = 0; double p = 0; uint64_t seed = 0; };
+struct TrajDev { uint32_t asz, s0; double p; uint64_t seed; };
 
 struct Engine {
   gs_params prm{};
@@ -67,6 +68,10 @@ struct Engine {
   std::vector<TrajTab> traj;
   uint32_t T = 1;
   size_t t_rows = 0, t_ents = 0;
+  // The tables' Philox keys differ (gs_create_traj_seeds): each table then has its own fail ranks
+  // (frank [T][N]) and, on the multi-source BFS, failure classes (mv_fcls [T][N]); t_frank is the
+  // stride of both, 0 when one array serves every table (equal keys: today's layout).
+  size_t t_frank = 0;
   uint32_t* stab = nullptr;      // [S] table of each slot (T > 1 only)
   TrajDev* ttab = nullptr;       // [T] (T > 1 only)
   std::vector<uint32_t> h_stab;  // host copy of stab (all zero for one table)
@@ -136,7 +141,7 @@ struct Engine {
   uint32_t* mv_ctr = nullptr;     // [4] records used
   unsigned long long* mv_pool = nullptr;  // [nbf][pcap] records of the round per fine bin
   uint32_t* mv_pused = nullptr;   // [nbf]
-  uint8_t* mv_fcls = nullptr;     // [N] failure class per node
+  uint8_t* mv_fcls = nullptr;     // [N] failure class per node ([T][N] when the tables' keys differ)
   uint8_t* mv_fk = nullptr;       // [S] failure class index per slot
   uint32_t* mv_thr = nullptr;     // [S] distinct failure counts (scratch)
   uint32_t* mv_hlvl = nullptr;    // host-mapped [256] frontier sizes (host pointer)
@@ -294,7 +299,7 @@ struct Engine {
 // launchers (gs_kernels.hip, gs_round_wg.hip); all enqueue on e.st and return hipError_t
 hipError_t launch_prefix_weights(Engine& e);
 hipError_t launch_init_entries(Engine& e);
-hipError_t launch_fail_keys(Engine& e, uint64_t* keys, uint32_t* ids);
+hipError_t launch_fail_keys(Engine& e, uint64_t seed, uint64_t* keys, uint32_t* ids);
 hipError_t launch_scatter_rank(Engine& e, const uint32_t* sorted_ids, uint32_t* rank_out);
 hipError_t launch_clear_slot_masks(Engine& e, uint32_t table, uint32_t node, uint32_t bucket, uint32_t bits);
 hipError_t launch_bfs(Engine& e, bool record);

@@ -118,7 +118,7 @@ hipError_t launch_init_entries(Engine& e) {
   for (uint32_t t = 0; t < e.T; ++t)  // every trajectory table draws the same INIT streams with its own size
     GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_init_entries<A>, dim3(grid_for(total, 256)), dim3(256), 0, e.st,
                                                 e.bucket, e.P, e.IX, e.peers + t * e.t_rows, e.hl + t * e.t_ents, e.N,
-                                                e.traj[t].asz, e.prm.seed));
+                                                e.traj[t].asz, e.traj[t].seed));
   hipError_t r = hipGetLastError();
   return r != hipSuccess ? r : launch_own_rows(e, nullptr, nullptr);
 }
@@ -131,8 +131,8 @@ __global__ void k_fail_keys(uint32_t N, uint64_t seed, uint64_t* keys, uint32_t*
   keys[v] = s.next();
   ids[v] = v;
 }
-hipError_t launch_fail_keys(Engine& e, uint64_t* keys, uint32_t* ids) {
-  hipLaunchKernelGGL(k_fail_keys, dim3(grid_for(e.N, 256)), dim3(256), 0, e.st, e.N, e.prm.seed, keys, ids);
+hipError_t launch_fail_keys(Engine& e, uint64_t seed, uint64_t* keys, uint32_t* ids) {
+  hipLaunchKernelGGL(k_fail_keys, dim3(grid_for(e.N, 256)), dim3(256), 0, e.st, e.N, seed, keys, ids);
   return hipGetLastError();
 }
 __global__ void k_scatter_rank(uint32_t N, const uint32_t* sorted_ids, uint32_t* rank) {
@@ -314,25 +314,27 @@ hipError_t launch_rotate(Engine& e, uint32_t round, bool defer_clear) {
     uint32_t* changed = e.rot_changed + t * e.t_ents;
     const uint32_t asz = e.traj[t].asz;
     const double p = e.traj[t].p;
+    const uint64_t seed = e.traj[t].seed;  // the table's own key
     if (zero_cnt) {
       hipError_t r = hipMemsetAsync(cnt, 0, sizeof(uint32_t), e.st);
       if (r != hipSuccess) return r;
     }
     if (e.N <= RS_MAX) {
       GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_small<A>, dim3(1), dim3(1024), 0, e.st, e.bucket, e.P, e.IX,
-                                                  peers, hl, list, cnt, cnt_other, changed, e.N, asz, e.prm.seed, round, p));
+                                                  peers, hl, list, cnt, cnt_other, changed, e.N, asz, seed, round, p));
     } else if (!rot_split) {
       const uint32_t grid = (e.N + RF_NODES - 1) / RF_NODES;
       GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_fused<A>, dim3(grid), dim3(RF_THREADS), 0, e.st, e.bucket,
                                                   e.P, e.IX, peers, hl, list, cnt, cnt_other, changed, e.N, asz,
-                                                  e.prm.seed, round, p, e.ORW, e.mv_fcls,
+                                                  seed, round, p, e.ORW,
+                                                  e.mv_fcls ? e.mv_fcls + t * e.t_frank : nullptr,
                                                   e.own ? e.own + t * e.own_ts : nullptr));
     } else {
-      hipLaunchKernelGGL(k_rotate_decide, dim3(grid_for(e.N, 4096, 256)), dim3(1024), 0, e.st, e.N, e.prm.seed, round,
+      hipLaunchKernelGGL(k_rotate_decide, dim3(grid_for(e.N, 4096, 256)), dim3(1024), 0, e.st, e.N, seed, round,
                          p, list, cnt, cnt_other);
       GS_ASZP_DISPATCH(e.ASZP, hipLaunchKernelGGL(k_rotate_entries<A>, dim3(grid_for((size_t)e.N * NB, 256, 2048)),
                                                   dim3(256), 0, e.st, e.bucket, e.P, e.IX, peers, hl, list, cnt, changed,
-                                                  e.N, asz, e.prm.seed, round));
+                                                  e.N, asz, seed, round));
     }
   }
   if (e.N <= RS_MAX || rot_split) {  // (the fused kernel refreshed its nodes' own rows itself)
@@ -626,6 +628,7 @@ hipError_t launch_bfs(Engine& e, bool record) {
       BfsArgs b = a;
       if (e.T > 1) {  // (slot-major layout; inb / PAIRS keep the engine's row stride)
         b.peers = e.peers + t * e.t_rows; b.hl = e.hl + t * e.t_ents; b.ASZ = tt.asz; b.S = tt.ns;
+        b.frank = e.frank + t * e.t_frank;  // (its own fail ranks when the tables' keys differ)
         b.origin += s0; b.obkt += s0; b.nfail += s0; if (b.sfan) b.sfan += s0;
         b.mask += p0; b.hops += p0; b.cnt += p0; b.inb += p0; b.egress += p0; b.egress_acc += p0; b.strand += p0;
         b.bm += s0 * e.bm_words; b.rs_u32 += s0 * 4; b.rs_ssum += s0; b.rs_hist += s0 * 256;
@@ -872,6 +875,7 @@ struct StatsArgs {
   uint32_t* bm_cnt;  // [S][64] set bits per chunk of each slot's bitmap (k_bm_count)
   gs_round_summary* sum;
   uint32_t N, S, W;
+  uint32_t o0;      // TB passes: the first slot of the launch's trajectory table
   uint32_t lo, hi;  // nodes of this pass (a node-range partition passes its own range)
   uint32_t NP, vlo; // pair p = slot * NP + (node - vlo); egress at slot * eso + (node - vlo) * esu
   size_t eso, esu;  // egress strides of (slot, node)
@@ -884,10 +888,13 @@ struct StatsArgs {
 // together: a thread's trip is a chain of dependent loads (hop, then egress and the
 // accumulators), and one node per trip left the pass bound by loads in flight (C5: 16 x
 // 10M pairs in ~0.7 ms).
+// TB: one launch per trajectory table whose fail ranks are its own (the tables' keys differ):
+// a.frank is that table's array and the grid's slots start at a.o0. Every other engine runs
+// the TB = false forms, which read neither.
 constexpr uint32_t SP_UN = 4;
-template <bool FULL, bool EG = false>
+template <bool FULL, bool EG = false, bool TB = false>
 __global__ __launch_bounds__(256) void k_stats_pass(StatsArgs a) {
-  const uint32_t o = blockIdx.x, bx = blockIdx.y, gxn = gridDim.y;
+  const uint32_t o = TB ? blockIdx.x + a.o0 : blockIdx.x, bx = blockIdx.y, gxn = gridDim.y;
   const size_t base = (size_t)o * a.NP - a.vlo;
   const uint32_t nf = a.nfail[o];
   __shared__ uint32_t h[256];
@@ -1131,7 +1138,18 @@ hipError_t launch_stats(Engine& e, uint32_t rec_slot, int mode) {
   a.hi = e.vlo + e.NP;
   a.NP = e.NP; a.vlo = e.vlo;
   uint32_t gx = grid_for(e.NP, 256 * SP_UN, std::max<uint32_t>(64, 2048 / std::max<uint32_t>(e.S, 1)));
-  if (mode == 0 || mode == 3) hipLaunchKernelGGL(k_stats_pass<true>, dim3(e.S, gx), dim3(256), 0, e.st, a);
+  a.o0 = 0;
+  if (e.t_frank) {  // per table, on its own fail ranks (stranded = unreached and not failed)
+    for (uint32_t t = 0; t < e.T; ++t) {
+      const TrajTab& tt = e.traj[t];
+      a.frank = e.frank + t * e.t_frank;
+      a.o0 = tt.s0;
+      const dim3 g(tt.ns, gx);
+      if (mode == 0 || mode == 3) hipLaunchKernelGGL((k_stats_pass<true, false, true>), g, dim3(256), 0, e.st, a);
+      else if (mode == 1) hipLaunchKernelGGL((k_stats_pass<false, false, true>), g, dim3(256), 0, e.st, a);
+      else if (mode == 4 || mode == 5) hipLaunchKernelGGL((k_stats_pass<false, true, true>), g, dim3(256), 0, e.st, a);
+    }
+  } else if (mode == 0 || mode == 3) hipLaunchKernelGGL(k_stats_pass<true>, dim3(e.S, gx), dim3(256), 0, e.st, a);
   else if (mode == 1) hipLaunchKernelGGL(k_stats_pass<false>, dim3(e.S, gx), dim3(256), 0, e.st, a);
   else if (mode == 4 || mode == 5) hipLaunchKernelGGL((k_stats_pass<false, true>), dim3(e.S, gx), dim3(256), 0, e.st, a);
   if (mode != 3 && mode != 5)  // the pass only (a partition sums the partials over ranks first)

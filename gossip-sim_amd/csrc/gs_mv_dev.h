@@ -78,9 +78,10 @@ struct MvArgs {
   // slot o's entries are table stab[o]'s, of ring size ttab[t].asz; table t's peers / hl / own rows
   // lie t * t_rows / t * t_ents / t * own_ts words (entries) after table 0's. ASZ stays the
   // capacity: the stride of a slice's run in the record area.
+  // fcls holds the tables' failure classes t_fcls bytes apart (0: one array, the tables' keys are equal).
   const uint32_t* stab;
   const TrajDev* ttab;
-  size_t t_rows, t_ents, own_ts;
+  size_t t_rows, t_ents, own_ts, t_fcls;
 };
 
 // Entry b of expand run (T row) w: b = 0 the run's base in the record area, b = 1 + c its
@@ -264,7 +265,7 @@ __device__ __forceinline__ void mv_expand_entry(const MvArgs& a, uint2 ent, cons
     hv = (MT ? a.hl + tb * a.t_ents : a.hl)[ent_i];
     load_row<ASZP>((MT ? a.peers + tb * a.t_rows : a.peers) + (size_t)ent_i * ASZP, row);
 #pragma unroll
-    for (int s = 0; s < ASZP; ++s) fc[s] = a.any_fail ? a.fcls[row[s]] : 0xFFu;
+    for (int s = 0; s < ASZP; ++s) fc[s] = a.any_fail ? (MT ? a.fcls + tb * a.t_fcls : a.fcls)[row[s]] : 0xFFu;
   }
   const uint32_t head = hv & 0xFF, len = hv >> 8;
   uint32_t plain = 0, pc0 = 0, pc1 = 0, pc2 = 0, pc3 = 0, pc4 = 0;  // (plain slots' push counts, bit-sliced)

@@ -116,10 +116,12 @@ struct RoundArgs {
   // several trajectory tables (the MT kernels; else null): slot o reads table stab[o] -- peers / hl /
   // rpeers / rhl hold the tables t_rows words / t_ents entries apart, the rotation lists N words,
   // the changed bits t_ents words and the counters 2 words apart -- with ttab[t]'s size and
-  // probability; rot_on is then the number of tables (one leading rotation workgroup each)
+  // probability; rot_on is then the number of tables (one leading rotation workgroup each).
+  // ttab[t].seed is the table's Philox key (the MT kernels draw DECIDE and ROTATE on it) and frank
+  // holds the tables' fail ranks t_frank words apart (0: one array, the tables' keys are equal)
   const uint32_t* stab;
   const TrajDev* ttab;
-  size_t t_rows, t_ents;
+  size_t t_rows, t_ents, t_frank;
 };
 
 // Phase clock: thread 0 adds the time since the last mark to phase_clk[ph].
@@ -740,11 +742,13 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
       if (a.plist) { a.plist += (size_t)t * N; a.pcount += 2 * t; }
       a.ASZ = a.ttab[t].asz;
       a.rp = a.ttab[t].p;
+      a.seed = a.ttab[t].seed;  // the table's own key: DECIDE and ROTATE
       rotate_ahead_wg<ASZP>(a, reinterpret_cast<uint32_t*>(smem));
       return;
     }
     const uint32_t t = a.stab[blockIdx.x - a.rot_on];
     a.peers += t * a.t_rows; a.hl += t * a.t_ents;
+    a.frank += t * a.t_frank;  // the table's own FAIL ranks
     a.ASZ = a.ttab[t].asz;
     if (a.rot_count) {  // the pending clear of this table's last rotation
       a.rot_list += (size_t)t * N; a.rot_count += 2 * t; a.rot_changed += t * a.t_ents;
@@ -1218,7 +1222,8 @@ hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_c
   RoundArgs a;
   a.rot_on = ra ? e.T : 0u;  // (one leading rotation workgroup per trajectory table)
   a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents;
-  a.P = e.P; a.IX = e.IX; a.seed = e.prm.seed; a.rp = e.traj[0].p;
+  a.t_frank = e.t_frank;
+  a.P = e.P; a.IX = e.IX; a.seed = e.traj[0].seed; a.rp = e.traj[0].p;
   a.rpeers = ra ? ra->peers2 : nullptr; a.rhl = ra ? ra->hl2 : nullptr;
   a.rlist = ra ? ra->list : nullptr; a.rcount = ra ? ra->count : nullptr; a.rchanged = ra ? ra->changed : nullptr;
   a.plist = ra ? ra->plist : nullptr; a.pcount = ra ? ra->pcount : nullptr;

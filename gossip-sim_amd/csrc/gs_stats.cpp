@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/gossip_hip.h"
+#include "gs_traj_plan.h"
 
 namespace {
 
@@ -205,11 +206,11 @@ int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_
 }
 
 // The sims as slots of one engine: with traj (>= 2 tables, the sims already grouped in slot
-// order) a gs_create_traj engine, else the gs_create engine at cfg's size and probability.
+// order) a gs_create_traj engine (with tab_seeds, a key per table), else the gs_create engine at cfg's size and probability.
 static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                     const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                     const double* fractions, const uint32_t* fanouts, const gs_traj* traj, uint32_t n_traj,
-                    gs_sim_result** out) {
+                    const uint64_t* tab_seeds, gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
   gs_params prm{};
@@ -226,7 +227,7 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
     for (uint32_t t = 0; t < n_traj; ++t) prm.active_set_size = std::max(prm.active_set_size, traj[t].active_set_size);
     // bfs_mode GS_BFS_MULTI names the multi-source table engine (any other mode behaves as before)
     if (cfg->bfs_mode == GS_BFS_MULTI) prm.flags |= GS_FLAG_TRAJ_MULTI;
-    r = gs_create_traj(&prm, stakes, n, n_sims, traj, n_traj, &e);
+    r = gs_create_traj_seeds(&prm, stakes, n, n_sims, traj, n_traj, tab_seeds, &e);  // (null seeds: gs_create_traj)
   } else {
     r = gs_create(&prm, stakes, n, n_sims, &e);
   }
@@ -382,43 +383,35 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
 int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                                const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                                const double* fractions, const uint32_t* fanouts, gs_sim_result** out) {
-  return run_sims(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, out);
+  return run_sims(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, nullptr, out);
 }
 
-// A value of active-set size and rotation probability per sim: the sims are grouped by
-// (size, probability) into trajectory tables -- equal pairs need not be adjacent -- run in
-// table order as slots of one engine, and the results come back in sim order.
-int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+// A value of active-set size, rotation probability and (seeds != null) Philox seed per sim: the
+// sims are grouped into trajectory tables (gs_traj_plan.h), run in table order as slots of one
+// engine, and the results come back in sim order.
+static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                             const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                             const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
-                            const double* rotation_probabilities, gs_sim_result** out) {
-  if (!active_set_sizes && !rotation_probabilities)
-    return gs_run_simulations_fanouts(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
-                                      out);
+                            const double* rotation_probabilities, const uint64_t* seeds, gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
-  std::vector<gs_traj> tabs;
-  std::vector<uint32_t> tab_of(n_sims);
-  for (uint32_t i = 0; i < n_sims; ++i) {
-    const uint32_t a = active_set_sizes ? active_set_sizes[i] : cfg->active_set_size;
-    const double p = rotation_probabilities ? rotation_probabilities[i] : cfg->rotation_probability;
-    uint32_t t = 0;
-    while (t < tabs.size() && !(tabs[t].active_set_size == a && tabs[t].rotation_probability == p)) ++t;
-    if (t == tabs.size()) tabs.push_back(gs_traj{a, p, 0});
-    tabs[t].n_slots += 1;
-    tab_of[i] = t;
-  }
-  if (tabs.size() == 1) {  // one value: exactly gs_run_simulations at it
+  const gs::TrajPlan pl = gs::traj_plan_build(n_sims, active_set_sizes, rotation_probabilities, seeds,
+                                              cfg->active_set_size, cfg->rotation_probability, cfg->seed);
+  if (pl.tabs.size() == 1) {  // one value: exactly gs_run_simulations at it
     gs_sim_config c = *cfg;
-    c.active_set_size = tabs[0].active_set_size;
-    c.rotation_probability = tabs[0].rotation_probability;
+    c.active_set_size = pl.tabs[0].asz;
+    c.rotation_probability = pl.tabs[0].p;
+    c.seed = pl.tabs[0].seed;
     return gs_run_simulations_fanouts(&c, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
                                       out);
   }
-  std::vector<uint32_t> sim_of;  // slot -> sim, in table order (stable within a table)
-  for (uint32_t t = 0; t < tabs.size(); ++t)
-    for (uint32_t i = 0; i < n_sims; ++i)
-      if (tab_of[i] == t) sim_of.push_back(i);
+  std::vector<gs_traj> tabs;
+  std::vector<uint64_t> tseeds;
+  for (const gs::TrajPlanTab& t : pl.tabs) {
+    tabs.push_back(gs_traj{t.asz, t.p, t.n_slots});
+    tseeds.push_back(t.seed);
+  }
+  const std::vector<uint32_t>& sim_of = pl.sim_of;
   std::vector<uint32_t> orr(n_sims), mi(n_sims), fo(n_sims);
   std::vector<double> th(n_sims), fr(n_sims);
   for (uint32_t s = 0; s < n_sims; ++s) {
@@ -431,13 +424,37 @@ int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, ui
   }
   gs_sim_result* res = nullptr;
   const int r = run_sims(cfg, stakes, n, n_sims, orr.data(), mi.data(), th.data(), fr.data(), fanouts ? fo.data() : nullptr,
-                         tabs.data(), (uint32_t)tabs.size(), &res);
+                         tabs.data(), (uint32_t)tabs.size(), seeds ? tseeds.data() : nullptr, &res);
   if (r) return r;
   std::vector<SimStats> by_sim(n_sims);
   for (uint32_t s = 0; s < n_sims; ++s) by_sim[sim_of[s]] = std::move(res->sims[s]);
   res->sims = std::move(by_sim);
   *out = res;
   return GS_OK;
+}
+
+int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                            const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                            const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
+                            const double* rotation_probabilities, gs_sim_result** out) {
+  if (!active_set_sizes && !rotation_probabilities)
+    return gs_run_simulations_fanouts(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                                      out);
+  return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                          active_set_sizes, rotation_probabilities, nullptr, out);
+}
+
+// ... and a Philox seed per sim (seeds == NULL: exactly gs_run_simulations_traj): the tables are
+// the distinct (size, probability, seed) triples, each drawing on its own key.
+int gs_run_simulations_seeds(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                             const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                             const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
+                             const double* rotation_probabilities, const uint64_t* seeds, gs_sim_result** out) {
+  if (!seeds)
+    return gs_run_simulations_traj(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                                   active_set_sizes, rotation_probabilities, out);
+  return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                          active_set_sizes, rotation_probabilities, seeds, out);
 }
 
 }  // extern "C"

@@ -28,6 +28,11 @@ rank's whole share of such a sweep runs as one engine (run_simulations(aszs=, ro
 when the network fits the workgroup engine (`traj_supported`); otherwise the share runs as
 `run_sweep` does, one engine per value -- or, with multi=True, as one multi-source table
 engine (bfs_mode GS_BFS_MULTI) at any node count that BFS supports (`traj_multi_supported`).
+
+`run_trial_sweep` repeats a sweep at several seeds: a table also carries its own Philox key
+(gs_create_traj_seeds, run_simulations(seeds=)), so a rank's share of (value, seed) units is one
+engine under the same rules (`trial_batchable`). `run_traj_sweep` keeps treating differing
+seeds as a reason for per-value engines.
 """
 import numpy as np
 
@@ -337,3 +342,72 @@ def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_de
             res = runner(stakes, n_sims=1, **kw)
             local[i] = {(kind, name): (res.f64(0, name) if kind == "f" else res.u64(0, name)) for kind, name in NAMES}
     return allreduce_results(local, len(values), group=group, device=comm_device)
+
+
+def _trial_mergeable(cfgs):
+    """_traj_mergeable with `seed` counted as a per-table key: a trajectory table carries its own
+    Philox seed (gs_create_traj_seeds), so configurations whose seeds differ still merge."""
+    return _traj_mergeable([{k: v for k, v in c.items() if k != "seed"} for c in cfgs])
+
+
+def trial_batchable(cfgs, n_nodes):
+    """traj_batchable for (value, seed) units: the kwargs may differ in seed as well as in
+    asz / p / fanout (and the per-sim lists); the network rule is the same (seeds do not enter
+    the geometry)."""
+    if not _trial_mergeable(cfgs):
+        return False
+    return traj_supported(n_nodes, max(c.get("fanout", 6) for c in cfgs), max(c.get("asz", 12) for c in cfgs))[0]
+
+
+def trial_batchable_multi(cfgs, n_nodes):
+    """traj_batchable_multi for (value, seed) units: seed is a per-table key."""
+    if not _trial_mergeable(cfgs):
+        return False
+    return traj_multi_supported(n_nodes, len(cfgs), max(c.get("fanout", 6) for c in cfgs),
+                                max(c.get("asz", 12) for c in cfgs))
+
+
+def run_trial_sweep(stakes, values, seeds, make_cfg, *, group=None, device=None, comm_device=None, runner=None,
+                    multi=False):
+    """A sweep repeated at several seeds (the reference's users repeat a configuration and look
+    at the spread; here a repeat is a seed). Units are (value, seed) pairs, value-major: result
+    index i_value * len(seeds) + i_seed. make_cfg(value) -> kwargs of run_simulations for that
+    value (its `seed`, if any, is replaced by the unit's); values=[None] is plain replicas of
+    make_cfg(None). Units are dealt round-robin over the ranks (shard) and each rank's share runs
+    as ONE engine with a table per (size, probability, seed) when trial_batchable -- or, with
+    multi=True, trial_batchable_multi (bfs_mode GS_BFS_MULTI) -- else one engine per unit.
+    Results are bit-identical either way."""
+    tdist, rank, world = _dist_info(group)
+    runner = runner or run_simulations
+    seeds = [int(s) for s in seeds]
+    n_units = len(values) * len(seeds)
+    local = {}
+    mine = shard(n_units, rank, world)
+    cfgs = []
+    for i in mine:
+        c = dict(make_cfg(values[i // len(seeds)]))
+        c["seed"] = seeds[i % len(seeds)]
+        cfgs.append(c)
+    batch = len(mine) > 1 and trial_batchable(cfgs, len(stakes))
+    as_multi = multi and len(mine) > 1 and not batch and trial_batchable_multi(cfgs, len(stakes))
+    if batch or as_multi:
+        kw = {k: v for k, v in cfgs[0].items() if k not in _PER_TABLE and k != "seed"}
+        if as_multi:
+            kw["bfs_mode"] = GS_BFS_MULTI
+        for k in _PER_SIM:
+            if cfgs[0].get(k) is not None:
+                kw[k] = [x for c in cfgs for x in c[k]]
+        if device is not None:
+            kw["device"] = device
+        res = runner(stakes, n_sims=len(mine), fanouts=[int(c.get("fanout", 6)) for c in cfgs],
+                     aszs=[int(c.get("asz", 12)) for c in cfgs], rot_probs=[float(c.get("p", 0.013333)) for c in cfgs],
+                     seeds=[c["seed"] for c in cfgs], **kw)
+        for j, i in enumerate(mine):
+            local[i] = {(kind, name): (res.f64(j, name) if kind == "f" else res.u64(j, name)) for kind, name in NAMES}
+    else:
+        for i, kw in zip(mine, cfgs):
+            if device is not None:
+                kw["device"] = device
+            res = runner(stakes, n_sims=1, **kw)
+            local[i] = {(kind, name): (res.f64(0, name) if kind == "f" else res.u64(0, name)) for kind, name in NAMES}
+    return allreduce_results(local, n_units, group=group, device=comm_device)

@@ -150,9 +150,20 @@ int gs_create(const gs_params* params, const uint64_t* stakes, uint32_t n_nodes,
  * next n1, ... fixed at create; the counts must sum to n_slots. params.active_set_size is
  * the capacity (1..32; row stride, push-mask width and LDS layout are sized by it, as
  * params.push_fanout sizes the per-slot fanouts) and every table's size is in [1, capacity];
- * params.rotation_probability is ignored. The seed is engine-wide: tables draw the INIT /
- * ROTATE / DECIDE streams a gs_create engine with that size and probability draws, so each
- * slot is bit-identical to its own per-value engine; the FAIL stream is shared. A prune
+ * params.rotation_probability is ignored. With gs_create_traj the seed is engine-wide: tables
+ * draw the INIT / ROTATE / DECIDE streams a gs_create engine with that size and probability
+ * draws, so each slot is bit-identical to its own per-value engine; the FAIL stream is shared.
+ * gs_create_traj_seeds gives every table its own Philox key: table t draws INIT, ROTATE,
+ * DECIDE and FAIL on seeds[t] (params.seed is ignored), so a slot of table t is bit-identical
+ * to a gs_create engine with seed seeds[t], that size and that probability -- seed replicas,
+ * and sweeps x replicas, run as one engine. seeds == NULL is exactly gs_create_traj; equal
+ * seeds give the gs_create_traj engine at that seed (one array of fail ranks, the same memory
+ * and kernels); otherwise every table holds its own fail ranks (4 B per node and table; the
+ * multi-source BFS one more byte) and gs_read_failed reads the slot's own table's. Duplicate
+ * (size, probability, seed) tables are allowed. Every rule below holds for both calls, and
+ * seeds do not enter gs_traj_supported / gs_traj_multi_supported. gs_engine_traj_seeds reads
+ * the keys back (GS_ERANGE and *n_traj when cap is too small): the engine's seed for every
+ * table of an engine made another way. A prune
  * mask's bits are physical ring slots of the slot's own table. bfs_mode must be
  * GS_BFS_WORKGROUP or GS_BFS_AUTO (which resolves to WORKGROUP whatever the slot count), and
  * the network must fit the workgroup engine's LDS (gs_traj_supported, host arithmetic only:
@@ -180,6 +191,10 @@ typedef struct gs_traj {
 int gs_create_traj(const gs_params* params, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_slots,
                    const gs_traj* traj, uint32_t n_traj, gs_engine** out);
 int gs_engine_traj(gs_engine* e, gs_traj* out, uint32_t cap, uint32_t* n_traj); /* reads the tables back */
+int gs_create_traj_seeds(const gs_params* params, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_slots,
+                         const gs_traj* traj, uint32_t n_traj, const uint64_t* seeds /*[n_traj] or NULL*/,
+                         gs_engine** out);
+int gs_engine_traj_seeds(gs_engine* e, uint64_t* out, uint32_t cap, uint32_t* n_traj);
 int gs_traj_supported(uint32_t n_nodes, uint32_t push_fanout, uint32_t max_active_set_size, int* fused);
 int gs_traj_multi_supported(uint32_t n_nodes, uint32_t n_slots, uint32_t push_fanout, uint32_t max_active_set_size);
 void gs_destroy(gs_engine* e);
@@ -411,6 +426,16 @@ int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, ui
                             const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                             const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
                             const double* rotation_probabilities, gs_sim_result** out);
+/* The same with a Philox seed per sim as well (seed replicas, and sweeps x replicas, as one
+ * engine): seeds == NULL is exactly gs_run_simulations_traj. Otherwise the sims are grouped by
+ * (size, probability, seed) into the tables of one gs_create_traj_seeds engine, permuted into
+ * table order and back; cfg->seed is unused. One distinct triple is gs_run_simulations_fanouts
+ * at that triple (cfg->seed replaced by the seed). */
+int gs_run_simulations_seeds(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_sims,
+                             const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                             const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
+                             const double* rotation_probabilities, const uint64_t* seeds /*per sim or NULL*/,
+                             gs_sim_result** out);
 void gs_result_free(gs_sim_result* r);
 /* Named arrays of a finished sim (same names as the oracle): e.g. "coverage",
  * "rmr", "coverage_stats", "stranded", "hops_hist" ... Returns the element
