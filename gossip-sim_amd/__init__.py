@@ -68,6 +68,20 @@ SUMMARY_DTYPE = np.dtype([(n, np.uint32 if t is C.c_uint32 else np.uint64) for n
 assert SUMMARY_DTYPE.itemsize == C.sizeof(RoundSummary)
 
 
+class ClusterRound(C.Structure):  # gs_cluster_round: one recorded round of the cluster load view
+    _fields_ = [("pushes", C.c_uint64), ("ingress", C.c_uint64), ("prunes", C.c_uint64), ("delivered", C.c_uint64),
+                ("egress_max", C.c_uint32), ("egress_max_node", C.c_uint32), ("ingress_max", C.c_uint32),
+                ("ingress_max_node", C.c_uint32), ("senders", C.c_uint32), ("pad0", C.c_uint32)]
+
+
+CLUSTER_ROUND_DTYPE = np.dtype([(n, np.uint32 if t is C.c_uint32 else np.uint64) for n, t in ClusterRound._fields_])
+assert CLUSTER_ROUND_DTYPE.itemsize == C.sizeof(ClusterRound)
+CLUSTER_TOTALS = ("egress", "ingress", "prunes", "delivered", "hop_sum")
+CLUSTER_RESULT_NAMES = tuple("cluster_" + k for k in CLUSTER_TOTALS + (
+    "egress_peak", "ingress_peak", "round_pushes", "round_egress_max", "round_egress_max_node", "round_ingress_max",
+    "round_ingress_max_node", "round_senders"))
+
+
 class SimConfig(C.Structure):
     _fields_ = [("push_fanout", C.c_uint32), ("active_set_size", C.c_uint32), ("iterations", C.c_uint32),
                 ("warm_up_rounds", C.c_uint32), ("min_ingress_nodes", C.c_uint32), ("when_to_fail", C.c_uint32),
@@ -127,6 +141,13 @@ EXPORTS = {
     "gs_run_simulations_seeds": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gs_run_simulations_cluster": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "gs_cluster_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_read_cluster_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "gs_read_cluster_rounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gs_destroy": (None, [C.c_void_p]),
     "gs_set_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "gs_set_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -560,6 +581,35 @@ class Engine:
         _check(lib().gs_read_accumulators(self.h, slot, _ptr(e), _ptr(i), _ptr(p), _ptr(st), _ptr(hh)))
         return e, i, p, st, hh
 
+    # --- cluster load view (per-node load summed over every slot) --------------
+    def enable_cluster_view(self, on=True):
+        """Allocates (or, on=False, frees) the cluster load view: from now on every recorded round
+        also sums the slots' egress / ingress / prunes / deliveries per node on the device."""
+        _check(lib().gs_cluster_enable(self.h, 1 if on else 0))
+
+    def cluster_load(self):
+        """Totals over the recorded rounds since set_slots -- egress, ingress, prunes, delivered,
+        hop_sum (u64 [n]) -- and the per-round peaks egress_peak, ingress_peak (u32 [n])."""
+        out = {k: np.zeros(self.n, dtype=np.uint64) for k in CLUSTER_TOTALS}
+        out["egress_peak"] = np.zeros(self.n, dtype=np.uint32)
+        out["ingress_peak"] = np.zeros(self.n, dtype=np.uint32)
+        _check(lib().gs_read_cluster_load(self.h, *[_ptr(out[k]) for k in CLUSTER_TOTALS], _ptr(out["egress_peak"]),
+                                          _ptr(out["ingress_peak"])))
+        return out
+
+    def cluster_rounds(self):
+        """One CLUSTER_ROUND_DTYPE record per recorded round (row r of summaries() is the same round)."""
+        cap = 1 << 12
+        while True:
+            out = np.zeros(cap, dtype=CLUSTER_ROUND_DTYPE)
+            cnt = C.c_size_t()
+            rc = lib().gs_read_cluster_rounds(self.h, _ptr(out), cap, C.byref(cnt))
+            if rc == -4 and cnt.value > cap:
+                cap = cnt.value
+                continue
+            _check(rc)
+            return out[:cnt.value]
+
     def failed(self, slot):
         out = np.zeros(self.n, dtype=np.uint8)
         _check(lib().gs_read_failed(self.h, slot, _ptr(out)))
@@ -620,14 +670,17 @@ class SimResult:
 def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, thresholds=None, fractions=None,
                     fanout=6, asz=12, iterations=1, warm_up=200, p=0.013333, thr=0.15, min_ingress_nodes=2,
                     fraction_to_fail=0.1, when_to_fail=0, nb_stranded=10, nb_message=5, nb_hops=15, test_type=0,
-                    seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None, aszs=None, rot_probs=None, seeds=None):
+                    seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None, aszs=None, rot_probs=None, seeds=None,
+                    cluster=False):
     """gossip_main.rs run_simulation for n_sims sims as slots of one engine.
     fanouts: a push fanout per sim (the engine's capacity is their maximum; `fanout` is unused then).
     aszs / rot_probs: an active-set size / rotation probability per sim (default `asz` / `p`); sims
     with equal pairs share a trajectory table of one engine, and results stay in sim order.
     seeds: a Philox seed per sim (`seed` is unused then): the tables are the distinct (size,
     probability, seed) triples, so seed replicas run as one engine, each sim equal to its own
-    run_simulations(seed=...) call."""
+    run_simulations(seed=...) call.
+    cluster: run the engine with its cluster load view on; the result then also answers
+    u64(sim, name) for CLUSTER_RESULT_NAMES (the same arrays under every sim)."""
     st = np.ascontiguousarray(stakes, dtype=np.uint64)
     cfg = SimConfig(fanout, asz, iterations, warm_up, min_ingress_nodes, when_to_fail, p, thr, fraction_to_fail,
                     nb_stranded, nb_message, nb_hops, test_type, seed, device, bfs_mode)
@@ -648,7 +701,14 @@ def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, th
     if sd is not None and sd.shape != (n_sims,):
         raise ValueError(f"run_simulations: seeds needs exactly n_sims = {n_sims} values")
     h = C.c_void_p()
-    if sd is not None:
+    if cluster:
+        _check(lib().gs_run_simulations_cluster(C.byref(cfg), _ptr(st), len(st), n_sims,
+                                                None if r is None else _ptr(r), None if mi is None else _ptr(mi),
+                                                None if th is None else _ptr(th), None if fr is None else _ptr(fr),
+                                                None if fo is None else _ptr(fo), None if az is None else _ptr(az),
+                                                None if rp is None else _ptr(rp), None if sd is None else _ptr(sd),
+                                                1, C.byref(h)))
+    elif sd is not None:
         _check(lib().gs_run_simulations_seeds(C.byref(cfg), _ptr(st), len(st), n_sims,
                                               None if r is None else _ptr(r), None if mi is None else _ptr(mi),
                                               None if th is None else _ptr(th), None if fr is None else _ptr(fr),

@@ -19,7 +19,8 @@
 // stake YAML (--accounts-from-yaml --account-file) or the deterministic synthetic
 // network (--synthetic N) instead of an RPC pull; --influx other than `n` is refused.
 // --save-results / --replay-results keep the named result arrays of a run in a text
-// file and print the report from it again without a GPU.
+// file and print the report from it again without a GPU. --cluster-load PATH runs every
+// engine with its cluster load view on and writes each node's load summed over all origins.
 #include <algorithm>
 #include <cerrno>
 #include <cinttypes>
@@ -46,6 +47,10 @@ const char* U64_NAMES[] = {"origin", "hop_max", "hop_min", "aggregate_hops", "ld
                            "stranded_round_count", "stranded_round_max", "stranded_round_min", "hops_hist",
                            "stranded_hist", "egress_hist", "ingress_hist", "prune_hist", "egress_cpb",
                            "validator_hist", "hist_errors", "failed_count", "rmr_m", "rmr_n"};
+// --cluster-load: the totals of the cluster load view (additive across engines; peaks and
+// per-round lines are not, and are not kept)
+const char* CLUSTER_NAMES[] = {"cluster_egress", "cluster_ingress", "cluster_prunes", "cluster_delivered",
+                               "cluster_hop_sum"};
 
 [[noreturn]] void die(int code, const std::string& msg) {
   std::fprintf(stderr, "error: %s\n", msg.c_str());
@@ -76,6 +81,7 @@ struct Cli {
   // engine / offline extensions
   uint64_t synthetic = 0, seed = 0x5EED0003ull, gpus = 1, bfs_mode = GS_BFS_AUTO;
   std::string save_results, replay_results, engine_plan;
+  std::string cluster_load;   // per-node load summed over every simulation of every engine
   std::string influx_file;  // offline Influx line protocol (gs_influx.cpp)
   uint64_t influx_time_base = 0;
   bool batch_sweeps = false;  // an active-set-size / rotate-probability / push-fanout sweep as one engine per device
@@ -100,6 +106,10 @@ void usage() {
       "  --synthetic N        the deterministic synthetic power-law network of N nodes instead of RPC\n"
       "  --seed S [0x5EED0003] --gpus K [1] --bfs-mode 0..5 [0 = auto; 1 workgroup, 2 level, 3 binned, 4 multi, 5 hybrid]\n"
       "  --save-results PATH  --replay-results PATH (print the report of a saved run, no GPU)\n"
+      "  --cluster-load PATH  run every engine with its cluster load view and write one line per node in id order:\n"
+      "                       pubkey,stake,egress,ingress,prunes,delivered,hop_sum -- the measured rounds' totals\n"
+      "                       summed over every simulation (origin) of every engine of the run; --save-results then\n"
+      "                       keeps these totals, and --replay-results with --cluster-load rewrites the file\n"
       "  --engine-plan PATH   write one line per engine: device, simulations, active-set size, fanouts\n"
       "  --batch-sweeps       run an active-set-size, rotate-probability or push-fanout sweep as ONE engine per\n"
       "                       device (an active-set table per value) instead of one engine per value; a plan\n"
@@ -182,6 +192,7 @@ Cli parse(int argc, char** argv) {
     else if (a == "--save-results") c.save_results = need(i);
     else if (a == "--replay-results") c.replay_results = need(i);
     else if (a == "--engine-plan") c.engine_plan = need(i);
+    else if (a == "--cluster-load") c.cluster_load = need(i);
     else if (a == "--influx-file") c.influx_file = need(i);
     else if (a == "--influx-time-base") u64(i, c.influx_time_base);
     else if (a == "--batch-sweeps") c.batch_sweeps = true;
@@ -238,12 +249,17 @@ struct Job {
 };
 
 void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsrep::SimArrays>& out,
-             std::string& err) {
+             std::string& err, bool cluster) {
   gs_sim_config cfg = j.cfg;
   cfg.device = j.device;
   gs_sim_result* r = nullptr;
   const int rc =
-      j.traj && !j.seeds.empty()
+      cluster ? gs_run_simulations_cluster(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+                                           j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(),
+                                           j.slot_fanouts || j.traj ? j.fanouts.data() : nullptr,
+                                           j.traj ? j.aszs.data() : nullptr, j.traj ? j.probs.data() : nullptr,
+                                           j.traj && !j.seeds.empty() ? j.seeds.data() : nullptr, 1, &r)
+      : j.traj && !j.seeds.empty()
           ? gs_run_simulations_seeds(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
                                      j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(), j.fanouts.data(),
                                      j.aszs.data(), j.probs.data(), j.seeds.data(), &r)
@@ -271,6 +287,13 @@ void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsre
       a.u[nm].resize(n);
       gs_result_u64(r, (uint32_t)k, nm, a.u[nm].data(), n);
     }
+    if (cluster && k == 0)  // the engine's totals once, under its first simulation
+      for (const char* nm : CLUSTER_NAMES) {
+        const size_t n = gs_result_u64(r, 0, nm, nullptr, 0);
+        if (n == SIZE_MAX) continue;
+        a.u[nm].resize(n);
+        gs_result_u64(r, 0, nm, a.u[nm].data(), n);
+      }
   }
   gs_result_free(r);
 }
@@ -568,7 +591,7 @@ int main(int argc, char** argv) {
           if ((uint64_t)j.device != d || !errs[d].empty()) continue;
           Job jj = j;
           jj.device = ndev > 0 ? (int)(d % (uint64_t)ndev) : 0;
-          run_job(jj, stakes, sims, errs[d]);
+          run_job(jj, stakes, sims, errs[d], !c.cluster_load.empty());
         }
       });
     for (auto& t : th) t.join();
@@ -582,6 +605,29 @@ int main(int argc, char** argv) {
   if (!c.save_results.empty()) {
     std::string err;
     if (!gsrep::save_results(c.save_results, sims, err)) die(1, err);
+  }
+  if (!c.cluster_load.empty()) {  // totals are additive: summed over every engine's (over --gpus workers too)
+    const size_t nn = stakes.size();
+    std::vector<std::vector<uint64_t>> tot(5, std::vector<uint64_t>(nn, 0));
+    bool any = false;
+    for (const auto& sm : sims)
+      for (size_t w = 0; w < 5; ++w) {
+        const auto it = sm.u.find(CLUSTER_NAMES[w]);
+        if (it == sm.u.end()) continue;
+        if (it->second.size() != nn)
+          die(1, std::string(CLUSTER_NAMES[w]) + " holds " + std::to_string(it->second.size()) + " nodes, not " +
+                     std::to_string(nn));
+        any = true;
+        for (size_t v = 0; v < nn; ++v) tot[w][v] += it->second[v];
+      }
+    if (!any && num_sims && !c.replay_results.empty())
+      die(1, c.replay_results + " holds no cluster_* totals (it was saved without --cluster-load)");
+    FILE* f = std::fopen(c.cluster_load.c_str(), "w");
+    if (!f) die(1, "cannot write " + c.cluster_load);
+    for (size_t v = 0; v < nn; ++v)
+      std::fprintf(f, "%s,%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 "\n", keys[v].c_str(),
+                   stakes[v], tot[0][v], tot[1][v], tot[2][v], tot[3][v], tot[4][v]);
+    std::fclose(f);
   }
   if (!c.influx_file.empty()) {  // the datapoint queue's text, in enqueue order (gossip_main.rs:372-645)
     gsrep::ReportInput in;

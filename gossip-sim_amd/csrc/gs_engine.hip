@@ -82,6 +82,7 @@ static int dalloc(Engine& e, T** p, size_t count, int fill = 0) {
 
 static int flush_rot_clear(Engine* e);
 static int ensure_rot_ahead(Engine* e);
+static int cluster_zero(Engine* e);
 
 template <class T>
 static void dfree(Engine& e, T*& p, size_t count) {
@@ -789,7 +790,8 @@ static int reset_pair_state(Engine* e) {
   HIPC(hipMemsetAsync(e->prune_round, 0, e->PAIRS, e->st));
   e->sum_used = 0;
   e->h_sum.clear();
-  return GS_OK;
+  e->h_cl.clear();
+  return cluster_zero(e);
 }
 
 int gs_set_slots(gs_engine* eh, const gs_slot* slots, uint32_t n_slots) {
@@ -1093,8 +1095,33 @@ static int drain_summaries(Engine* e) {
   size_t old = e->h_sum.size();
   e->h_sum.resize(old + n);
   HIPC(hipMemcpyAsync(e->h_sum.data() + old, e->sum, n * sizeof(gs_round_summary), hipMemcpyDeviceToHost, e->st));
+  if (e->cl_on) {  // the cluster view's entries of the same rounds (index r stays the same round in both)
+    const size_t co = e->h_cl.size();
+    e->h_cl.resize(co + e->sum_used);
+    HIPC(hipMemcpyAsync(e->h_cl.data() + co, e->cl_ring, e->sum_used * sizeof(gs_cluster_round), hipMemcpyDeviceToHost,
+                        e->st));
+    HIPC(hipMemsetAsync(e->cl_ring, 0, e->sum_used * sizeof(gs_cluster_round), e->st));
+    HIPC(hipStreamSynchronize(e->st));
+    for (size_t i = co; i < e->h_cl.size(); ++i) {  // k_cluster_fold's keys: max << 32 | ~node
+      gs_cluster_round& c = e->h_cl[i];
+      const uint32_t en = ~c.egress_max, em = c.egress_max_node, in = ~c.ingress_max, im = c.ingress_max_node;
+      c.egress_max = em; c.egress_max_node = en; c.ingress_max = im; c.ingress_max_node = in;
+    }
+  }
   HIPC(hipStreamSynchronize(e->st));
   e->sum_used = 0;
+  return GS_OK;
+}
+
+// The cluster load view's reduction of the recorded round that takes summary row sum_used:
+// behind the round's last kernel, before the row is counted (gs_cluster.hip).
+static int cluster_record(Engine* e) {
+  if (!e->cl_on) return GS_OK;
+  hipEvent_t t0;
+  e->tbegin("cluster", &t0);
+  hipError_t r = launch_cluster_view(*e, e->sum_used);
+  e->tend("cluster", t0);
+  HIPC(r);
   return GS_OK;
 }
 
@@ -1104,6 +1131,7 @@ static int do_stats(Engine* e, int mode) {
   hipError_t r = launch_stats(*e, e->sum_used, mode);
   e->tend("stats", t0);
   HIPC(r);
+  if (int s = cluster_record(e)) return s;
   if (++e->sum_used == e->sum_cap) return drain_summaries(e);
   return GS_OK;
 }
@@ -1178,6 +1206,8 @@ static int round_ahead(Engine* e, uint32_t round, bool rec) {
   e->rot_clear_pending = true;
   e->rot_cnt_dirty = true;  // (the other counter was not zeroed)
   e->inb_valid = false;
+  if (rec)
+    if (int s = cluster_record(e)) return s;
   if (rec && ++e->sum_used == e->sum_cap) return drain_summaries(e);
   return GS_OK;
 }
@@ -1202,6 +1232,8 @@ int gs_round(gs_engine* eh, uint32_t round, int record) {
     r = launch_rotate(*e, round, true);
     e->tend("rotate", t0);
     HIPC(r);
+    if (rec)
+      if (int s = cluster_record(e)) return s;
     if (rec && ++e->sum_used == e->sum_cap) return drain_summaries(e);
     return GS_OK;
   }
@@ -1523,6 +1555,85 @@ int gs_read_accumulators(gs_engine* eh, uint32_t slot, uint64_t* egress, uint64_
     if (ingress) ingress[o + v] = b[v];
     if (prunes) prunes[o + v] = c[v];
   }
+  return GS_OK;
+}
+
+// ------------------------------------------------- cluster load view ----
+static int cluster_zero(Engine* e) {
+  if (!e->cl_on) return GS_OK;
+  HIPC(hipMemsetAsync(e->cl_scr, 0, (size_t)5 * e->NP * 4, e->st));
+  HIPC(hipMemsetAsync(e->cl_tot, 0, (size_t)5 * e->NP * 8, e->st));
+  HIPC(hipMemsetAsync(e->cl_peak, 0, (size_t)2 * e->NP * 4, e->st));
+  HIPC(hipMemsetAsync(e->cl_ring, 0, (size_t)e->sum_cap * sizeof(gs_cluster_round), e->st));
+  return GS_OK;
+}
+
+static void cluster_free(Engine* e) {
+  dfree(*e, e->cl_scr, (size_t)5 * e->NP);
+  dfree(*e, e->cl_tot, (size_t)5 * e->NP);
+  dfree(*e, e->cl_peak, (size_t)2 * e->NP);
+  dfree(*e, e->cl_ring, (size_t)e->sum_cap);
+  e->cl_on = false;
+  e->h_cl.clear();
+}
+
+int gs_cluster_enable(gs_engine* eh, int on) {
+  ENGINE(eh);
+  if (e->part_on)
+    return fail(GS_ESTATE, "gs_cluster_enable: a node-range partition rank holds its own nodes' pairs only (the "
+                           "partitioned view needs an exchange of the per-round sums)");
+  if (!on) {
+    if (!e->cl_on) return GS_OK;
+    HIPC(hipStreamSynchronize(e->st));
+    cluster_free(e);
+    return GS_OK;
+  }
+  if (e->cl_on) return GS_OK;
+  // a round's per-node sums stay in u32: egress bytes and hops <= 255, in-degrees <= the inbound capacity
+  if ((uint64_t)e->S * std::max<uint64_t>(255, e->capin) >= (1ull << 32))
+    return fail(GS_ERANGE, "gs_cluster_enable: n_slots x max(255, inbound capacity) must stay below 2^32");
+  if (int s = drain_summaries(e)) return s;  // (the ring rows before now belong to rounds without the view)
+  int s = dalloc(*e, &e->cl_scr, (size_t)5 * e->NP, 0);
+  if (!s) s = dalloc(*e, &e->cl_tot, (size_t)5 * e->NP, 0);
+  if (!s) s = dalloc(*e, &e->cl_peak, (size_t)2 * e->NP, 0);
+  if (!s) s = dalloc(*e, &e->cl_ring, (size_t)e->sum_cap, 0);
+  if (s) {  // all four or none
+    const std::string msg = g_err;
+    HIPC(hipStreamSynchronize(e->st));
+    cluster_free(e);
+    return fail(s, msg);
+  }
+  e->cl_on = true;
+  e->h_cl.assign(e->h_sum.size() / e->S, gs_cluster_round{});
+  HIPC(hipStreamSynchronize(e->st));
+  return GS_OK;
+}
+
+int gs_read_cluster_load(gs_engine* eh, uint64_t* egress, uint64_t* ingress, uint64_t* prunes, uint64_t* delivered,
+                         uint64_t* hop_sum, uint32_t* egress_peak, uint32_t* ingress_peak) {
+  ENGINE(eh);
+  if (!e->cl_on) return fail(GS_ESTATE, "the cluster load view is not enabled (gs_cluster_enable)");
+  if (int s = check_err(e)) return s;
+  const size_t N = e->NP;
+  uint64_t* tot[5] = {egress, ingress, prunes, delivered, hop_sum};
+  for (int w = 0; w < 5; ++w)
+    if (tot[w]) HIPC(hipMemcpyAsync(tot[w], e->cl_tot + w * N, N * 8, hipMemcpyDeviceToHost, e->st));
+  if (egress_peak) HIPC(hipMemcpyAsync(egress_peak, e->cl_peak, N * 4, hipMemcpyDeviceToHost, e->st));
+  if (ingress_peak) HIPC(hipMemcpyAsync(ingress_peak, e->cl_peak + N, N * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  return GS_OK;
+}
+
+int gs_read_cluster_rounds(gs_engine* eh, gs_cluster_round* out, size_t cap, size_t* count) {
+  ENGINE(eh);
+  if (!e->cl_on) return fail(GS_ESTATE, "the cluster load view is not enabled (gs_cluster_enable)");
+  if (!count) return fail(GS_EINVAL, "null argument");
+  if (int s = check_err(e)) return s;
+  if (int s = drain_summaries(e)) return s;
+  *count = e->h_cl.size();
+  if (e->h_cl.size() > cap) return fail(GS_ERANGE, "cluster round buffer too small");
+  if (e->h_cl.size() && !out) return fail(GS_EINVAL, "null argument");
+  if (!e->h_cl.empty()) std::memcpy(out, e->h_cl.data(), e->h_cl.size() * sizeof(gs_cluster_round));
   return GS_OK;
 }
 

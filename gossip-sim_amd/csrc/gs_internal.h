@@ -252,6 +252,13 @@ struct Engine {
   gs_round_summary* sum = nullptr;  // device ring of recorded summaries [sum_cap][S]
   uint32_t sum_cap = 0, sum_used = 0;
   std::vector<gs_round_summary> h_sum;  // drained summaries
+  // cluster load view (gs_cluster_enable, gs_cluster.hip): per-node load summed over every slot
+  bool cl_on = false;
+  uint32_t* cl_scr = nullptr;          // [5][NP] this round's sums (zero between recorded rounds)
+  uint64_t* cl_tot = nullptr;          // [5][NP] egress, ingress, prunes, delivered, hop sum over recorded rounds
+  uint32_t* cl_peak = nullptr;         // [2][NP] largest egress / ingress of one recorded round
+  gs_cluster_round* cl_ring = nullptr; // [sum_cap] entry r belongs to summaries ring row r (raw keys: k_cluster_fold)
+  std::vector<gs_cluster_round> h_cl;  // drained entries (index = recorded round, like h_sum)
   uint32_t* err = nullptr;
   uint32_t* h_err = nullptr;  // pinned
   unsigned long long* phase_clk = nullptr;  // GS_PHASE_PROFILE=1: per-phase workgroup clock sums
@@ -390,6 +397,9 @@ hipError_t launch_stats(Engine& e, uint32_t rec_index, int mode);
 hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_index, bool rot_clear, const RotAhead* ra = nullptr);
 size_t round_wg_lds_bytes(uint32_t N, uint32_t fcap, uint32_t ASZP);
 size_t bfs_wg_lds_bytes(uint32_t N);
+// cluster load view (gs_cluster.hip): the recorded round's reduction over slots and its fold
+hipError_t launch_cluster_view(Engine& e, uint32_t rec_index);
+uint32_t cluster_chunk_slots(uint32_t NP, uint32_t S);
 hipError_t launch_gather_strided_u32(Engine& e, const uint32_t* src, size_t stride, uint32_t n, uint32_t* dst);
 
 }  // namespace gs

@@ -210,7 +210,7 @@ int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_
 static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                     const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                     const double* fractions, const uint32_t* fanouts, const gs_traj* traj, uint32_t n_traj,
-                    const uint64_t* tab_seeds, gs_sim_result** out) {
+                    const uint64_t* tab_seeds, int cluster, gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
   gs_params prm{};
@@ -245,6 +245,7 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
 #define CK(x) do { r = (x); if (r) { gs_destroy(e); return r; } } while (0)
   CK(gs_set_slots(e, slots.data(), n_sims));
   if (fanouts) CK(gs_set_slot_fanouts(e, fanouts));
+  if (cluster) CK(gs_cluster_enable(e, 1));  // the cluster load view over every sim of the engine
   CK(gs_init_active_sets(e));
   for (uint32_t it = 0; it < cfg->iterations; ++it) {
     if (cfg->test_type == 5 && it == cfg->when_to_fail) CK(gs_fail_nodes(e, frac.data()));
@@ -257,6 +258,28 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
   CK(gs_read_round_summaries(e, sums.data(), sums.size(), &nsum));
   std::unique_ptr<gs_sim_result> res(new gs_sim_result());  // released to *out only on success
   res->sims.resize(n_sims);
+  std::map<std::string, std::vector<uint64_t>> cl;  // the cluster view's arrays: the same under every sim
+  if (cluster) {
+    std::vector<uint64_t> tot[5];
+    for (auto& t : tot) t.resize(n);
+    std::vector<uint32_t> pe(n), pi(n);
+    CK(gs_read_cluster_load(e, tot[0].data(), tot[1].data(), tot[2].data(), tot[3].data(), tot[4].data(), pe.data(),
+                            pi.data()));
+    std::vector<gs_cluster_round> cr(rounds + 1);
+    size_t ncr = 0;
+    CK(gs_read_cluster_rounds(e, cr.data(), cr.size(), &ncr));
+    cl["cluster_egress"] = tot[0]; cl["cluster_ingress"] = tot[1]; cl["cluster_prunes"] = tot[2];
+    cl["cluster_delivered"] = tot[3]; cl["cluster_hop_sum"] = tot[4];
+    cl["cluster_egress_peak"].assign(pe.begin(), pe.end());
+    cl["cluster_ingress_peak"].assign(pi.begin(), pi.end());
+    std::vector<uint64_t>&rp = cl["cluster_round_pushes"], &rem = cl["cluster_round_egress_max"],
+                         &ren = cl["cluster_round_egress_max_node"], &rim = cl["cluster_round_ingress_max"],
+                         &rin = cl["cluster_round_ingress_max_node"], &rs = cl["cluster_round_senders"];
+    for (size_t k = 0; k < ncr; ++k) {
+      rp.push_back(cr[k].pushes); rem.push_back(cr[k].egress_max); ren.push_back(cr[k].egress_max_node);
+      rim.push_back(cr[k].ingress_max); rin.push_back(cr[k].ingress_max_node); rs.push_back(cr[k].senders);
+    }
+  }
   uint64_t max_stake = 0;
   for (uint32_t v = 0; v < n; ++v) max_stake = std::max(max_stake, stakes[v]);
   std::vector<uint64_t> eg(n), in(n), pr(n), hh(256);
@@ -264,6 +287,7 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
   std::vector<uint8_t> failed(n);
   for (uint32_t s = 0; s < n_sims; ++s) {
     SimStats& o = res->sims[s];
+    for (const auto& kv : cl) o.u[kv.first] = kv.second;
     CK(gs_read_accumulators(e, s, eg.data(), in.data(), pr.data(), st.data(), hh.data()));
     CK(gs_read_failed(e, s, failed.data()));
     std::vector<double> cov, rmr, br, hmean, hmed, smean, smed;
@@ -383,7 +407,8 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
 int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                                const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                                const double* fractions, const uint32_t* fanouts, gs_sim_result** out) {
-  return run_sims(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, nullptr, out);
+  return run_sims(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, nullptr, 0,
+                  out);
 }
 
 // A value of active-set size, rotation probability and (seeds != null) Philox seed per sim: the
@@ -392,7 +417,8 @@ int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes,
 static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                             const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                             const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
-                            const double* rotation_probabilities, const uint64_t* seeds, gs_sim_result** out) {
+                            const double* rotation_probabilities, const uint64_t* seeds, int cluster,
+                            gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
   const gs::TrajPlan pl = gs::traj_plan_build(n_sims, active_set_sizes, rotation_probabilities, seeds,
@@ -402,8 +428,8 @@ static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, ui
     c.active_set_size = pl.tabs[0].asz;
     c.rotation_probability = pl.tabs[0].p;
     c.seed = pl.tabs[0].seed;
-    return gs_run_simulations_fanouts(&c, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
-                                      out);
+    return run_sims(&c, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, nullptr,
+                    cluster, out);
   }
   std::vector<gs_traj> tabs;
   std::vector<uint64_t> tseeds;
@@ -424,7 +450,7 @@ static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, ui
   }
   gs_sim_result* res = nullptr;
   const int r = run_sims(cfg, stakes, n, n_sims, orr.data(), mi.data(), th.data(), fr.data(), fanouts ? fo.data() : nullptr,
-                         tabs.data(), (uint32_t)tabs.size(), seeds ? tseeds.data() : nullptr, &res);
+                         tabs.data(), (uint32_t)tabs.size(), seeds ? tseeds.data() : nullptr, cluster, &res);
   if (r) return r;
   std::vector<SimStats> by_sim(n_sims);
   for (uint32_t s = 0; s < n_sims; ++s) by_sim[sim_of[s]] = std::move(res->sims[s]);
@@ -441,7 +467,7 @@ int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, ui
     return gs_run_simulations_fanouts(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
                                       out);
   return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
-                          active_set_sizes, rotation_probabilities, nullptr, out);
+                          active_set_sizes, rotation_probabilities, nullptr, 0, out);
 }
 
 // ... and a Philox seed per sim (seeds == NULL: exactly gs_run_simulations_traj): the tables are
@@ -454,7 +480,21 @@ int gs_run_simulations_seeds(const gs_sim_config* cfg, const uint64_t* stakes, u
     return gs_run_simulations_traj(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
                                    active_set_sizes, rotation_probabilities, out);
   return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
-                          active_set_sizes, rotation_probabilities, seeds, out);
+                          active_set_sizes, rotation_probabilities, seeds, 0, out);
+}
+
+// ... and the cluster load view over the engine's sims (cluster == 0: exactly gs_run_simulations_seeds)
+int gs_run_simulations_cluster(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                               const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                               const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
+                               const double* rotation_probabilities, const uint64_t* seeds, int cluster,
+                               gs_sim_result** out) {
+  if (!cluster)
+    return gs_run_simulations_seeds(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                                    active_set_sizes, rotation_probabilities, seeds, out);
+  // (the grouping handles one table and null per-sim arrays alike)
+  return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                          active_set_sizes, rotation_probabilities, seeds, cluster, out);
 }
 
 }  // extern "C"

@@ -276,12 +276,55 @@ int gs_read_round_summaries(gs_engine* e, gs_round_summary* out, size_t cap, siz
 int gs_read_accumulators(gs_engine* e, uint32_t slot, uint64_t* egress, uint64_t* ingress, uint64_t* prunes,
                          uint32_t* stranded_times, uint64_t* hop_hist /*[256]*/);
 int gs_read_failed(gs_engine* e, uint32_t slot, uint8_t* failed /*[n]*/);
+/* --- cluster load view: per-node message load summed over every slot ---------
+ * The trackers above are per slot, as the reference's are per origin (gossip_stats.rs:359-461:
+ * one Cluster is one origin). When the slots are the origins of one configuration ("all
+ * origins"), what a node sends and receives in a round is the sum over the slots -- the load
+ * the push/prune protocol exists to bound. With eg_j / in_j / pr_j the arrays gs_read_counters
+ * returns for slot j (egress of an unreached node reads 0) and h_j gs_read_hops', a recorded
+ * round r has, per node v:
+ *   E_r[v] = sum_j eg_j[v]   I_r[v] = sum_j in_j[v]   P_r[v] = sum_j pr_j[v]
+ *   D_r[v] = #{j : 1 <= h_j[v] <= 254}  (deliveries: slots that reached v, v not their origin)
+ *   H_r[v] = the sum of those h_j[v]
+ * gs_read_cluster_load returns, over the recorded rounds since the last gs_set_slots (the
+ * accumulators' rule), the totals of E, I, P, D, H and the peaks max_r E_r[v], max_r I_r[v];
+ * gs_read_cluster_rounds one gs_cluster_round per recorded round, entry r being the round of
+ * gs_read_round_summaries' row r: the sums over v of E_r, I_r, P_r, D_r, the largest E_r[v]
+ * and I_r[v] with their nodes (the smallest id among equals) and the nodes with E_r[v] > 0.
+ * All integer sums and maxima: exact, whatever the order of the reduction.
+ * The view sums EVERY slot of the engine, whatever its table, fanout or threshold: it means
+ * "load" only when the slots are origins of one configuration. Slot groups and weights per
+ * origin are not provided.
+ * gs_cluster_enable(on != 0) allocates the view (about 68 B per node and 56 B per recorded
+ * round held on the device, counted in gs_engine_info's bytes and gs_engine_memory's
+ * other_bytes) and zeroes it; it is allowed whenever gs_set_slots is, before or after it;
+ * enabling an enabled view is a no-op; on == 0 frees it. gs_set_slots zeroes it. Rounds
+ * recorded before the view was enabled read as all-zero entries. While enabled, every
+ * recorded round (gs_round with record != 0 on every path, gs_record_round) runs the
+ * reduction as two launches of their own behind the round's last kernel (kernel family
+ * "cluster"); a round that is not recorded launches nothing, and an engine that never enables
+ * the view allocates and launches nothing. The reads without an enabled view, and
+ * gs_cluster_enable on a node-range partition rank (gs_create_part: the ranks' per-round sums
+ * would need an exchange), return GS_ESTATE; a geometry whose per-round sums could pass u32
+ * (n_slots x max(255, inbound capacity) >= 2^32) GS_ERANGE. No reference interface. */
+typedef struct gs_cluster_round {
+  uint64_t pushes, ingress, prunes, delivered;
+  uint32_t egress_max, egress_max_node, ingress_max, ingress_max_node;
+  uint32_t senders, pad0;
+} gs_cluster_round;
+int gs_cluster_enable(gs_engine* e, int on);
+int gs_read_cluster_load(gs_engine* e, uint64_t* egress, uint64_t* ingress, uint64_t* prunes,
+                         uint64_t* delivered, uint64_t* hop_sum,        /* [n] each, NULL = skip */
+                         uint32_t* egress_peak, uint32_t* ingress_peak);
+/* *count = recorded rounds so far; GS_ERANGE when cap is smaller */
+int gs_read_cluster_rounds(gs_engine* e, gs_cluster_round* out, size_t cap, size_t* count);
 /* Cluster::mst (gossip.rs:580-591): parent[v] = the node that first discovered v in the
  * reference's FIFO queue order, UINT32_MAX for the origin and unreached nodes (debug
  * readback after gs_run_gossip, n <= 262,144). */
 int gs_read_mst(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
 /* GS_FLAG_PROFILE: summed device time of a kernel family ("bfs", "consume",
- * "rotate", "stats") since the last reset, and its launch count. */
+ * "rotate", "stats", "cluster": the cluster load view's two launches per recorded round)
+ * since the last reset, and its launch count. */
 int gs_kernel_time(gs_engine* e, const char* family, double* ms, uint64_t* launches);
 int gs_kernel_time_reset(gs_engine* e);
 int gs_engine_info(gs_engine* e, uint32_t* n_nodes, uint32_t* n_slots, uint32_t* bfs_mode, uint64_t* device_bytes);
@@ -436,6 +479,19 @@ int gs_run_simulations_seeds(const gs_sim_config* cfg, const uint64_t* stakes, u
                              const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
                              const double* rotation_probabilities, const uint64_t* seeds /*per sim or NULL*/,
                              gs_sim_result** out);
+/* The same with the cluster load view: cluster == 0 is exactly gs_run_simulations_seeds;
+ * otherwise the engine's view is enabled (gs_cluster_enable) before gs_init_active_sets, and
+ * the result also answers gs_result_u64 for -- the same arrays under any valid sim, in node id
+ * order -- "cluster_egress", "cluster_ingress", "cluster_prunes", "cluster_delivered",
+ * "cluster_hop_sum", "cluster_egress_peak", "cluster_ingress_peak" ([n] each) and, one value
+ * per measured round, "cluster_round_pushes", "cluster_round_egress_max",
+ * "cluster_round_egress_max_node", "cluster_round_ingress_max", "cluster_round_ingress_max_node",
+ * "cluster_round_senders". Every other name reads what it reads with cluster == 0. */
+int gs_run_simulations_cluster(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes, uint32_t n_sims,
+                               const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
+                               const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
+                               const double* rotation_probabilities, const uint64_t* seeds /*per sim or NULL*/,
+                               int cluster, gs_sim_result** out);
 void gs_result_free(gs_sim_result* r);
 /* Named arrays of a finished sim (same names as the oracle): e.g. "coverage",
  * "rmr", "coverage_stats", "stranded", "hops_hist" ... Returns the element
