@@ -184,6 +184,7 @@ EXPORTS = {
     "gs_kernel_time_reset": (C.c_int, [C.c_void_p]),
     "gs_engine_round_kind": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "gs_engine_bfs_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "gs_engine_round_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "gs_engine_memory": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gs_engine_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint64)]),
@@ -366,9 +367,14 @@ class Engine:
         _check(lib().gs_engine_round_kind(self.h, C.byref(f)))
         pb, ob = C.c_uint64(), C.c_uint64()
         _check(lib().gs_engine_memory(self.h, C.byref(pb), C.byref(ob)))
+        sp = np.zeros(3, dtype=np.uint32)  # round split (GS_ROUND_SPLIT): on, slots of the two groups
+        fn = getattr(lib(), "gs_engine_round_split", None)  # (None: an A/B build of older sources)
+        if fn is not None:
+            _check(fn(self.h, _ptr(sp), 3))
         return {"n_nodes": n.value, "n_slots": s.value, "bfs_mode": m.value, "device_bytes": b.value,
                 "pair_bytes": pb.value, "other_bytes": ob.value, "fused_round": bool(f.value),
-                "bfs_persistent": bool(self.bfs_geometry()["persistent_wgs"])}
+                "bfs_persistent": bool(self.bfs_geometry()["persistent_wgs"]),
+                "round_split": bool(sp[0]), "round_split_groups": [int(sp[1]), int(sp[2])] if sp[0] else []}
 
     def bfs_geometry(self):
         """Multi / hybrid BFS geometry (diagnostics): expand slice, coarse and fine bins, group width, groups."""

@@ -120,6 +120,7 @@ static int hb_alloc(Engine* e, uint32_t parts) {
 
 static void destroy_engine(Engine* e) {
   if (!e) return;
+  if (e->st2) hipStreamSynchronize(e->st2);
   if (e->st) hipStreamSynchronize(e->st);
   for (void* p : e->allocs) hipFree(p);
   if (e->h_err) hipHostFree(e->h_err);
@@ -132,6 +133,10 @@ static void destroy_engine(Engine* e) {
   for (auto& kv : e->timers)
     for (auto& pr : kv.second.ev) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
   for (hipEvent_t x : e->ev_pool) hipEventDestroy(x);
+  for (hipEvent_t x : {e->split_ev0[0], e->split_ev0[1], e->split_ev0[2], e->split_ev1[0], e->split_ev1[1],
+                       e->split_ev1[2], e->split_evj, e->split_t0, e->split_t1[0], e->split_t1[1]})
+    if (x) hipEventDestroy(x);
+  if (e->st2) hipStreamDestroy(e->st2);
   if (e->st) hipStreamDestroy(e->st);
   delete e;
 }
@@ -401,6 +406,27 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   // rotation ahead of the fused round (one-workgroup rotation sizes; GS_ROT_AHEAD=0: off)
   e->rot_ahead_ok = e->fused && n <= 16384 && round_wg_lds_bytes(n, e->fcap, e->ASZP) >= 4 * ((size_t)n + 1) &&
                     !(std::getenv("GS_ROT_AHEAD") && std::getenv("GS_ROT_AHEAD")[0] == '0');
+  // round split (Engine::split_ok): two slot groups on two streams. Only where a launch has a
+  // drain to hide -- at least twice as many slots as workgroups fit on the chip (two per CU: 12
+  // waves each at 6 per SIMD, LDS allowing) -- and only the single-table fused round with its
+  // rotation ahead, no partition, no phase clocks. GS_ROUND_SPLIT=0: off; =force: any S >= 2 (tests)
+  {
+    const char* x = std::getenv("GS_ROUND_SPLIT");
+    const bool off = x && x[0] == '0', force = x && std::strcmp(x, "force") == 0;
+    const char* pp = std::getenv("GS_PHASE_PROFILE");
+    hipDeviceProp_t dp;
+    size_t resident = 0;
+    if (!off && !force && hipGetDeviceProperties(&dp, prm->device) == hipSuccess)
+      resident = (size_t)dp.multiProcessorCount *
+                 std::min<size_t>(2, std::max<size_t>(1, (160 * 1024) / round_wg_lds_bytes(n, e->fcap, e->ASZP)));
+    e->split_ok = !off && e->rot_ahead_ok && e->T == 1 && !part && !(pp && pp[0] == '1') && n_slots >= 2 &&
+                  (force || (resident && n_slots >= 2 * resident));
+    if (e->split_ok) {
+      uint32_t pct = 50;  // group 0's share of the slots (GS_ROUND_SPLIT_PCT: measurements)
+      if (const char* q = std::getenv("GS_ROUND_SPLIT_PCT")) pct = std::min(90u, std::max(10u, (uint32_t)std::strtoul(q, nullptr, 10)));
+      e->split_s0 = std::min<uint32_t>(n_slots - 1, std::max<uint32_t>(1, (uint32_t)(((uint64_t)n_slots * pct + 50) / 100)));
+    }
+  }
 
   const size_t N = n, S = n_slots, PAIRS = e->PAIRS, NP = e->NP;
   e->SP = (uint32_t)((S + 3) & ~(size_t)3);
@@ -557,7 +583,7 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   e->h_nfail_any.assign(S, 0);
   ALLOC(e->lvl, 512, 0);  // [256] level sizes; binned BFS: [256 + d] = 1 iff level d was binned this round
   ALLOC(e->rot_list, e->T * N, 0);
-  ALLOC(e->rot_count, 2 * (size_t)e->T, 0);
+  ALLOC(e->rot_count, e->split_ok ? 3 : 2 * (size_t)e->T, 0);  // (round split: three generations, one table)
   ALLOC(e->rot_changed, e->T * e->t_ents, 0);
   ALLOC(e->rs_u32, S * 4, 0);
   ALLOC(e->rs_ssum, S, 0);
@@ -592,6 +618,22 @@ static int create_engine(const gs_params* prm, const uint64_t* stakes, uint32_t 
   if (const char* pp = std::getenv("GS_PHASE_PROFILE"); pp && pp[0] == '1') ALLOC(e->phase_clk, 32, 0);
   if (e->rot_ahead_ok) {  // the rotation-ahead buffers at create: counted in the engine's memory, fail here
     if (int s_ = ensure_rot_ahead(e)) { destroy_engine(e); return s_; }
+  }
+  if (e->split_ok) {  // the second stream, the third generation and the events, or no split at all
+    ALLOC(e->rows3[2], e->t_rows, 0);
+    ALLOC(e->hl3[2], e->t_ents, 0);
+    ALLOC(e->rot_list_b[2], N, 0);
+    ALLOC(e->rot_changed_b[2], e->t_ents, 0);
+    e->rows3[0] = e->peers; e->rows3[1] = e->peers2;
+    e->hl3[0] = e->hl; e->hl3[1] = e->hl2;
+    bool ok = hipStreamCreateWithFlags(&e->st2, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < 3 && ok; ++i)
+      ok = hipEventCreateWithFlags(&e->split_ev0[i], hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&e->split_ev1[i], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&e->split_evj, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreate(&e->split_t0) == hipSuccess && hipEventCreate(&e->split_t1[0]) == hipSuccess &&
+         hipEventCreate(&e->split_t1[1]) == hipSuccess;
+    if (!ok) { destroy_engine(e); return fail(GS_EHIP, "round split: stream / event creation"); }
   }
 
   // stakes, buckets and the static rotation prefix sums
@@ -764,11 +806,25 @@ int gs_engine_traj_seeds(gs_engine* eh, uint64_t* out, uint32_t cap, uint32_t* n
 
 void gs_destroy(gs_engine* eh) { destroy_engine(reinterpret_cast<Engine*>(eh)); }
 
-#define ENGINE(eh)                                                                           \
+// Round split: the primary stream waits for the second group's launches. Every entry point but
+// the split round itself starts here (ENGINE), so whatever it enqueues on `st`, reads back or
+// synchronizes sees both groups' rounds, and an error either group raised is on `st` by then.
+static int split_join(Engine* e) {
+  if (!e->split_open) return GS_OK;
+  HIPC(hipEventRecord(e->split_evj, e->st2));
+  HIPC(hipStreamWaitEvent(e->st, e->split_evj, 0));
+  e->split_open = false;
+  return GS_OK;
+}
+
+#define ENGINE_NOJOIN(eh)                                                                    \
   Engine* e = reinterpret_cast<Engine*>(eh);                                                 \
   if (!e) return fail(GS_EINVAL, "null engine");                                             \
   if (e->broken) return fail(GS_ESTATE, "engine unusable after a grid-barrier timeout; destroy it"); \
   HIPC(hipSetDevice(e->prm.device));
+#define ENGINE(eh)     \
+  ENGINE_NOJOIN(eh)    \
+  if (int js_ = split_join(e)) return js_;
 
 // Zeroes every prune mask (in the multi BFS's node lines, only the mask words).
 static hipError_t clear_masks(Engine* e) {
@@ -1212,13 +1268,100 @@ static int round_ahead(Engine* e, uint32_t round, bool rec) {
   return GS_OK;
 }
 
+// The split round (Engine::split_ok; gs_split_plan.h): group 0 -- with the rotation workgroup --
+// on `st`, group 1 on `st2`, each launch behind the events its generations need. Nothing here
+// waits on the host. The engine's own view (peers / hl, the last rotation's list, changed bits
+// and counter index, the pending clear) is kept as the single-stream round leaves it, so every
+// other entry point, which joins first, goes on unchanged.
+static int round_split(Engine* e, uint32_t round, bool rec) {
+  if (e->rows2_stale || !e->split_live) {  // the rows changed in place (or first round): equal generations
+    if (int s = split_join(e)) return s;
+    if (int s = flush_rot_clear(e)) return s;  // (the lists restart: the pending clear runs now)
+    int cur = 0;
+    while (cur < 2 && e->rows3[cur] != e->peers) ++cur;
+    if (e->rows3[cur] != e->peers) return fail(GS_ESTATE, "round split: unknown row buffer");
+    for (int g = 0; g < 3; ++g) {
+      if (g == cur) continue;
+      HIPC(hipMemcpyAsync(e->rows3[g], e->peers, e->t_rows * 4, hipMemcpyDeviceToDevice, e->st));
+      HIPC(hipMemcpyAsync(e->hl3[g], e->hl, e->t_ents * 2, hipMemcpyDeviceToDevice, e->st));
+    }
+    e->split_pl.reset(cur);
+    e->rows2_stale = false;
+    e->rows2_pending = -1;
+    e->split_live = true;
+  }
+  const SplitStep sp = e->split_pl.next();
+  RotAhead ra;
+  ra.peers2 = e->rows3[sp.write];
+  ra.hl2 = e->hl3[sp.write];
+  ra.list = e->rot_list_b[sp.list];
+  ra.changed = e->rot_changed_b[sp.list];
+  ra.count = e->rot_count + sp.list;
+  ra.plist = sp.catch1 >= 0 ? e->rot_list_b[sp.catch1] : nullptr;
+  ra.pcount = e->rot_count + (sp.catch1 >= 0 ? sp.catch1 : 0);
+  ra.plist2 = sp.catch2 >= 0 ? e->rot_list_b[sp.catch2] : nullptr;
+  ra.pcount2 = e->rot_count + (sp.catch2 >= 0 ? sp.catch2 : 0);
+  ra.round = round;
+  // (e->peers / e->hl are generation sp.read; a pending clear is the last rotation's, catch1)
+  const bool clr = e->rot_clear_pending;
+  const bool timed = (e->prm.flags & GS_FLAG_PROFILE) && family_timed(*e, "round");
+  const int k3 = (int)((e->split_pl.k - 1) % 3);  // this round's events
+  // group 0: after group 1's round k - 2 (which read the generation this rotation writes)
+  if (sp.g0_waits_g1 >= 0 && e->split_ev1_set[sp.g0_waits_g1 % 3])
+    HIPC(hipStreamWaitEvent(e->st, e->split_ev1[sp.g0_waits_g1 % 3], 0));
+  if (!e->split_open) {  // st2 joins in: behind everything `st` holds now (group 0's last round included)
+    HIPC(hipEventRecord(e->split_evj, e->st));
+    HIPC(hipStreamWaitEvent(e->st2, e->split_evj, 0));
+    e->split_open = true;
+  } else if (sp.g1_waits_g0 >= 0) {  // group 1: after group 0's round k - 1, whose rotation wrote these rows
+    HIPC(hipStreamWaitEvent(e->st2, e->split_ev0[sp.g1_waits_g0 % 3], 0));
+  }
+  if (timed && e->split_t_n == 0) HIPC(hipEventRecord(e->split_t0, e->st));
+  const SplitLaunch g0{0u, e->split_s0, e->st, true}, g1{e->split_s0, e->S - e->split_s0, e->st2, false};
+  hipError_t r = launch_round_wg(*e, rec, e->sum_used, clr, &ra, &g0);
+  if (r == hipSuccess) r = hipEventRecord(e->split_ev0[k3], e->st);
+  if (r == hipSuccess) r = launch_round_wg(*e, rec, e->sum_used, clr, &ra, &g1);
+  if (r == hipSuccess) r = hipEventRecord(e->split_ev1[k3], e->st2);
+  HIPC(r);
+  e->split_ev1_set[k3] = true;
+  if (timed) {
+    HIPC(hipEventRecord(e->split_t1[0], e->st));
+    HIPC(hipEventRecord(e->split_t1[1], e->st2));
+    e->split_t_n += 1;
+  }
+  e->peers = e->rows3[sp.write];
+  e->hl = e->hl3[sp.write];
+  e->rot_list = ra.list;
+  e->rot_changed = ra.changed;
+  e->rot_parity = (uint32_t)sp.list;  // (the index of the last rotation's counter)
+  e->rot_have_prev = true;
+  e->rot_clear_pending = true;
+  e->rot_cnt_dirty = true;
+  e->inb_valid = false;
+  if (rec && ++e->sum_used == e->sum_cap) {
+    if (int s = split_join(e)) return s;
+    return drain_summaries(e);
+  }
+  return GS_OK;
+}
+
 int gs_round(gs_engine* eh, uint32_t round, int record) {
-  ENGINE(eh);
+  ENGINE_NOJOIN(eh);
+  if (e->split_ok && e->fused && !e->cl_on && !e->part_on && round < (1u << 27) && e->slots_set)
+    return round_split(e, round, record != 0);
+  if (int s = split_join(e)) return s;
   if (int s = refuse_part(e)) return s;
   if (int s = need_slots(e)) return s;
   const bool rec = record != 0;
   if (e->fused) {  // BFS + consume + prune + statistics in one kernel per slot
     if (round >= (1u << 27)) return fail(GS_ERANGE, "round index must be < 2^27");
+    if (e->split_live) {  // (a split engine on this path: the cluster view came on) back to two row buffers
+      e->split_live = false;
+      e->rows2_stale = true;
+      const int o = e->peers == e->rows3[0] ? 1 : 0;
+      e->peers2 = e->rows3[o];
+      e->hl2 = e->hl3[o];
+    }
     if (e->rot_ahead_ok && !(e->rot_have_prev && (round & 1u) == e->rot_parity)) return round_ahead(e, round, rec);
     hipEvent_t t0;
     e->tbegin("round", &t0);
@@ -1664,6 +1807,16 @@ int gs_kernel_time(gs_engine* eh, const char* family, double* ms, uint64_t* laun
     *launches = e->timers["round"].n;
     return GS_OK;
   }
+  if (family && std::strcmp(family, "round") == 0 && e->split_t_n) {
+    // split rounds: the two groups' launches overlap, so not a sum over launches but the span from
+    // the first start to the later of the groups' last stops since the reset; one count per round
+    float x0 = 0, x1 = 0;
+    HIPC(hipEventElapsedTime(&x0, e->split_t0, e->split_t1[0]));
+    HIPC(hipEventElapsedTime(&x1, e->split_t0, e->split_t1[1]));
+    *ms = std::max(x0, x1);
+    *launches = e->split_t_n;
+    return GS_OK;
+  }
   auto it = e->timers.find(family ? family : "");
   *ms = 0;
   *launches = 0;
@@ -1692,6 +1845,7 @@ int gs_kernel_time_reset(gs_engine* eh) {
     kv.second.ms = 0;
     kv.second.n = 0;
   }
+  e->split_t_n = 0;
   if (e->phase_clk) HIPC(hipMemsetAsync(e->phase_clk, 0, 256, e->st));
   return GS_OK;
 }
@@ -1700,6 +1854,16 @@ int gs_engine_round_kind(gs_engine* eh, uint32_t* fused) {
   ENGINE(eh);
   if (!fused) return fail(GS_EINVAL, "null argument");
   *fused = e->fused ? 1u : 0u;
+  return GS_OK;
+}
+
+int gs_engine_round_split(gs_engine* eh, uint32_t* out, size_t n) {
+  ENGINE(eh);
+  if (!out || n < 3) return fail(GS_EINVAL, "gs_engine_round_split: need 3 words");
+  const bool on = e->split_ok && e->fused && !e->cl_on && !e->part_on;  // (what gs_round checks)
+  out[0] = on ? 1u : 0u;
+  out[1] = on ? e->split_s0 : 0u;
+  out[2] = on ? e->S - e->split_s0 : 0u;
   return GS_OK;
 }
 

@@ -9,6 +9,7 @@
 
 #include "../../include/gossip_hip.h"
 #include "gs_mv_groups.h"
+#include "gs_split_plan.h"
 
 namespace gs {
 
@@ -203,8 +204,31 @@ struct Engine {
   int rows2_pending = -1;           // parity of the rotation applied to peers but not peers2
   uint32_t* peers2 = nullptr;
   uint16_t* hl2 = nullptr;
-  uint32_t* rot_list_b[2] = {nullptr, nullptr};
-  uint32_t* rot_changed_b[2] = {nullptr, nullptr};
+  uint32_t* rot_list_b[3] = {nullptr, nullptr, nullptr};     // ([2]: round split only)
+  uint32_t* rot_changed_b[3] = {nullptr, nullptr, nullptr};
+  // Round split (GS_ROUND_SPLIT; gs_round on an eligible engine): the slots run as two groups,
+  // [0, split_s0) on `st` and [split_s0, S) on `st2`, one launch each per round, so that one
+  // group's workgroups fill the CUs the other's launch leaves idle while it drains. Group 0's
+  // launch carries the rotation workgroup. The groups may be one round apart, so rows, rotation
+  // lists, changed bits and counters have three generations (gs_split_plan.h); rot_count is then
+  // [3] and rot_parity the index of the last rotation's counter. Ordering is by events only:
+  // group 0's round k waits for group 1's round k - 2, group 1's round k for group 0's k - 1.
+  bool split_ok = false;            // eligible at create (the cluster view is checked per round)
+  uint32_t split_s0 = 0;            // slots of group 0
+  hipStream_t st2 = nullptr;
+  bool split_open = false;          // st2 holds work `st` has not waited for (split_join)
+  bool split_live = false;          // the three generations are coherent (a split round ran last on them)
+  SplitPlan split_pl;               // which generation each round reads and writes
+  uint32_t* rows3[3] = {nullptr, nullptr, nullptr};  // the row generations
+  uint16_t* hl3[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t split_ev0[3] = {nullptr, nullptr, nullptr};  // end of group 0's round k (k % 3)
+  hipEvent_t split_ev1[3] = {nullptr, nullptr, nullptr};  // end of group 1's round k
+  bool split_ev1_set[3] = {false, false, false};
+  hipEvent_t split_evj = nullptr;   // open / join
+  // kernel_time("round") with the split on: the span from the first launch's start to the last
+  // stop of either group since the reset, over split_t_n rounds
+  hipEvent_t split_t0 = nullptr, split_t1[2] = {nullptr, nullptr};
+  uint64_t split_t_n = 0;
 
   size_t rwg_attr_lds = 0;          // dynamic LDS the round kernel was last configured for
   bool rwg_attr_prof = false;       // ... and for which instantiation (phase clocks or not,
@@ -377,6 +401,15 @@ struct RotAhead {
   const uint32_t* plist;     // the previous ahead rotation's nodes (to copy first; null: none)
   const uint32_t* pcount;
   uint32_t round;
+  const uint32_t* plist2 = nullptr;  // round split: the ahead rotation before that one (null: none)
+  const uint32_t* pcount2 = nullptr;
+};
+// One slot group's launch of a split round: its slots, its stream, and whether it carries the
+// rotation workgroup (group 0 only).
+struct SplitLaunch {
+  uint32_t s0, ns;
+  hipStream_t st;
+  bool rot;
 };
 hipError_t launch_consume_prune(Engine& e, bool consume, bool prune, bool apply, bool record);
 hipError_t launch_consume_prune_g(Engine& e, bool record, bool consume = true, bool zero_slot_prunes = false);
@@ -394,7 +427,8 @@ hipError_t launch_part_dense_apply(Engine& e, const uint32_t* dense);  // masks 
 hipError_t launch_rotate(Engine& e, uint32_t round, bool defer_clear);
 hipError_t launch_rotate_clear(Engine& e);
 hipError_t launch_stats(Engine& e, uint32_t rec_index, int mode);
-hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_index, bool rot_clear, const RotAhead* ra = nullptr);
+hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_index, bool rot_clear, const RotAhead* ra = nullptr,
+                           const SplitLaunch* sl = nullptr);
 size_t round_wg_lds_bytes(uint32_t N, uint32_t fcap, uint32_t ASZP);
 size_t bfs_wg_lds_bytes(uint32_t N);
 // cluster load view (gs_cluster.hip): the recorded round's reduction over slots and its fold

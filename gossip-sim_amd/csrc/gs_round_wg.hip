@@ -122,6 +122,11 @@ struct RoundArgs {
   const uint32_t* stab;
   const TrajDev* ttab;
   size_t t_rows, t_ents, t_frank;
+  // round split (last, so that every other argument keeps its place): the ahead rotation before
+  // plist's, whose entries the rotation workgroup copies too -- with three row generations the
+  // other buffer is two rotations behind the current one (null: one rotation, or none)
+  const uint32_t* plist2;
+  const uint32_t* pcount2;
 };
 
 // Phase clock: thread 0 adds the time since the last mark to phase_clk[ph].
@@ -680,10 +685,14 @@ template <int ASZP>
 __device__ void rotate_ahead_wg(const RoundArgs& a, uint32_t* lids) {
   const uint32_t tid = threadIdx.x, T = blockDim.x, N = a.N;
   uint32_t& lcount = lids[N];
-  if (a.plist) {
-    const uint32_t total = *a.pcount * NB;
+  // (round split: the other buffer is two rotations behind; a node in both lists is copied twice,
+  // the same words from the same source)
+  for (int q = 0; q < 2; ++q) {
+    const uint32_t* pl = q ? a.plist2 : a.plist;
+    if (!pl) continue;
+    const uint32_t total = *(q ? a.pcount2 : a.pcount) * NB;
     for (uint32_t gid = tid; gid < total; gid += T) {
-      const uint32_t ent = a.plist[gid / NB] * NB + gid % NB;
+      const uint32_t ent = pl[gid / NB] * NB + gid % NB;
 #pragma unroll
       for (int w = 0; w < ASZP; ++w) a.rpeers[(size_t)ent * ASZP + w] = a.peers[(size_t)ent * ASZP + w];
       a.rhl[ent] = a.hl[ent];
@@ -1180,8 +1189,11 @@ __global__ __launch_bounds__(RWG_THREADS, RWG_MIN_WAVES) void k_round_wg(RoundAr
   RWG_MARK(6);
 }
 
+// workgroups of the launch and its stream (the whole engine on e.st, or one slot group of a split round)
+struct RwgGrid { uint32_t blocks; hipStream_t st; };
+
 template <int ASZP, bool OFF16, int FP, bool PROF, bool PF, bool MT = false>
-static hipError_t launch_rwg_p(Engine& e, const RoundArgs& a, size_t lds) {
+static hipError_t launch_rwg_p(Engine& e, const RoundArgs& a, size_t lds, const RwgGrid& g) {
   if (e.rwg_attr_lds != lds || e.rwg_attr_prof != PROF || e.rwg_attr_pf != PF || e.rwg_attr_mt != MT) {
     hipError_t r = hipFuncSetAttribute((const void*)k_round_wg<ASZP, OFF16, FP, PROF, PF, MT>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1191,42 +1203,44 @@ static hipError_t launch_rwg_p(Engine& e, const RoundArgs& a, size_t lds) {
     e.rwg_attr_pf = PF;
     e.rwg_attr_mt = MT;
   }
-  hipLaunchKernelGGL((k_round_wg<ASZP, OFF16, FP, PROF, PF, MT>), dim3(e.S + a.rot_on), dim3(RWG_THREADS), lds, e.st, a);
+  hipLaunchKernelGGL((k_round_wg<ASZP, OFF16, FP, PROF, PF, MT>), dim3(g.blocks), dim3(RWG_THREADS), lds, g.st, a);
   return hipSuccess;
 }
 
 template <int ASZP, bool OFF16, int FP>
-static hipError_t launch_rwg_fp(Engine& e, const RoundArgs& a, size_t lds) {
+static hipError_t launch_rwg_fp(Engine& e, const RoundArgs& a, size_t lds, const RwgGrid& g) {
   if constexpr (ASZP == 12 && OFF16 && FP == 6) {  // C2's shape: phase clocks available
-    if (a.phase_clk && !a.sfan && !a.stab) return launch_rwg_p<ASZP, OFF16, FP, true, false>(e, a, lds);
+    if (a.phase_clk && !a.sfan && !a.stab) return launch_rwg_p<ASZP, OFF16, FP, true, false>(e, a, lds, g);
   }
   // several trajectory tables: the kernels that rebase onto their workgroup's table (the single-table
   // kernels are unchanged); the per-slot fanouts compose with them
   if (a.stab)
-    return a.sfan ? launch_rwg_p<ASZP, OFF16, FP, false, true, true>(e, a, lds)
-                  : launch_rwg_p<ASZP, OFF16, FP, false, false, true>(e, a, lds);
+    return a.sfan ? launch_rwg_p<ASZP, OFF16, FP, false, true, true>(e, a, lds, g)
+                  : launch_rwg_p<ASZP, OFF16, FP, false, false, true>(e, a, lds, g);
   // slots of different fanouts: the kernel that loads its slot's own (the uniform kernel is unchanged)
-  if (a.sfan) return launch_rwg_p<ASZP, OFF16, FP, false, true>(e, a, lds);
-  return launch_rwg_p<ASZP, OFF16, FP, false, false>(e, a, lds);
+  if (a.sfan) return launch_rwg_p<ASZP, OFF16, FP, false, true>(e, a, lds, g);
+  return launch_rwg_p<ASZP, OFF16, FP, false, false>(e, a, lds, g);
 }
 
 template <int ASZP, bool OFF16>
-static hipError_t launch_rwg(Engine& e, const RoundArgs& a, size_t lds) {
+static hipError_t launch_rwg(Engine& e, const RoundArgs& a, size_t lds, const RwgGrid& g) {
   // FP: compacted pushes per lane (fanout <= 6, the reference's default, or the ring)
   constexpr int FP6 = ASZP < 6 ? ASZP : 6;
-  if (a.fcap <= (uint32_t)FP6) return launch_rwg_fp<ASZP, OFF16, FP6>(e, a, lds);
-  return launch_rwg_fp<ASZP, OFF16, ASZP>(e, a, lds);
+  if (a.fcap <= (uint32_t)FP6) return launch_rwg_fp<ASZP, OFF16, FP6>(e, a, lds, g);
+  return launch_rwg_fp<ASZP, OFF16, ASZP>(e, a, lds, g);
 }
 
-hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_clear, const RotAhead* ra) {
+hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_clear, const RotAhead* ra,
+                           const SplitLaunch* sl) {
   RoundArgs a;
-  a.rot_on = ra ? e.T : 0u;  // (one leading rotation workgroup per trajectory table)
+  a.rot_on = ra && (!sl || sl->rot) ? e.T : 0u;  // (one leading rotation workgroup per trajectory table)
   a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents;
   a.t_frank = e.t_frank;
   a.P = e.P; a.IX = e.IX; a.seed = e.traj[0].seed; a.rp = e.traj[0].p;
   a.rpeers = ra ? ra->peers2 : nullptr; a.rhl = ra ? ra->hl2 : nullptr;
   a.rlist = ra ? ra->list : nullptr; a.rcount = ra ? ra->count : nullptr; a.rchanged = ra ? ra->changed : nullptr;
   a.plist = ra ? ra->plist : nullptr; a.pcount = ra ? ra->pcount : nullptr;
+  a.plist2 = ra ? ra->plist2 : nullptr; a.pcount2 = ra ? ra->pcount2 : nullptr;
   a.rround = ra ? ra->round : 0u;
   a.stake = e.stake; a.bucket = e.bucket; a.peers = e.peers; a.hl = e.hl; a.frank = e.frank; a.srank = e.srank;
   a.by_srank = e.by_srank; a.prank = e.prank; a.by_prank = e.by_prank; a.pstake = e.pstake; a.rinfo = e.rinfo; a.origin = e.origin;
@@ -1241,10 +1255,24 @@ hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_c
   a.err = e.err; a.phase_clk = e.phase_clk;
   a.wave_c_max = (e.prm.flags & GS_FLAG_NARROW_WAVE_PATH) ? 24u : 64u; a.N = e.N; a.S = e.S; a.ASZ = e.ASZ; a.fanout = e.fanout; a.sfan = e.fvar ? e.sfan : nullptr; a.fcap = e.fcap; a.PAIRS = e.PAIRS;
   a.record = record ? 1 : 0;
+  RwgGrid g{e.S + a.rot_on, e.st};
+  if (sl) {  // one slot group: the kernel's slot index starts at 0, so everything it indexes by slot
+             // or by (slot, node) pair starts at the group's first slot (ckey keeps its PAIRS stride)
+    const size_t s0 = sl->s0, p0 = s0 * e.N;
+    a.origin += s0; a.obkt += s0; a.nfail += s0; a.min_ingress += s0; a.thr += s0; a.slot_prunes += s0;
+    if (a.sum) a.sum += s0;
+    if (a.sfan) a.sfan += s0;
+    a.hist_acc += 256 * s0;
+    a.hops += p0; a.cnt += p0; a.mask += p0; a.cmeta += p0; a.ckey += p0; a.egress += p0; a.prune_round += p0;
+    a.egress_acc += p0; a.ingress_acc += p0; a.prune_acc += p0; a.strand += p0;
+    a.S = sl->ns;
+    g.blocks = sl->ns + a.rot_on;
+    g.st = sl->st;
+  }
   const size_t lds = round_wg_lds_bytes(e.N, e.fcap, e.ASZP);
   hipError_t r;
   const bool off16 = rwg_off16(e.N, e.fcap);
-  GS_ASZP_DISPATCH(e.ASZP, r = (off16 ? launch_rwg<A, true>(e, a, lds) : launch_rwg<A, false>(e, a, lds)));
+  GS_ASZP_DISPATCH(e.ASZP, r = (off16 ? launch_rwg<A, true>(e, a, lds, g) : launch_rwg<A, false>(e, a, lds, g)));
   if (r != hipSuccess) return r;
   return hipGetLastError();
 }

@@ -335,6 +335,13 @@ int gs_engine_memory(gs_engine* e, uint64_t* pair_bytes, uint64_t* other_bytes);
 /* 1 if gs_round runs the one-kernel workgroup round (BFS, consume, prune and
  * statistics per slot in one workgroup), 0 if it launches the step kernels. */
 int gs_engine_round_kind(gs_engine* e, uint32_t* fused);
+/* Round split (GS_ROUND_SPLIT, default on; =0 off): gs_round on a one-kernel engine with one
+ * trajectory table, no cluster view, no partition and at least twice as many slots as round
+ * workgroups fit on the device launches the slots as two groups on two streams, so one group's
+ * workgroups fill the compute units the other's launch leaves idle while it ends. Results are
+ * the single-stream round's, bit for bit. out[0] 1 if gs_round splits now, out[1] / out[2] the
+ * slots of the two groups (zeros when off). n >= 3. */
+int gs_engine_round_split(gs_engine* e, uint32_t* out, size_t n);
 /* Geometry of the multi-source / hybrid BFS (diagnostics; not a reference interface): out[0]
  * frontier entries (multi) or nodes (hybrid) per expand slice, out[1] coarse destination bins,
  * out[2] fine bins, out[3] slots per slot group, out[4] slot groups; with n >= 6, out[5] the

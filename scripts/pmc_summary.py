@@ -43,10 +43,17 @@ def main():
     ap.add_argument("--kernel", default="k_round_wg")
     ap.add_argument("--launches", type=int, default=100)
     ap.add_argument("--bench-args", default="")
+    ap.add_argument("--per-round", type=int, default=1,
+                    help="launches of the kernel per round (2 with the round split on): their counters are "
+                         "summed, so a `launch` below is a round either way and --launches counts rounds")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     fetch = per_dispatch(os.path.join(a.dir, "fetch", "run_counter_collection.csv"), a.kernel, "FETCH_SIZE")
     write = per_dispatch(os.path.join(a.dir, "write", "run_counter_collection.csv"), a.kernel, "WRITE_SIZE")
+    if a.per_round > 1:
+        n = a.per_round
+        fetch = [sum(fetch[i:i + n]) for i in range(len(fetch) % n, len(fetch), n)]
+        write = [sum(write[i:i + n]) for i in range(len(write) % n, len(write), n)]
     fetch, write = fetch[-a.launches:], write[-a.launches:]
     fk = sum(fetch) / len(fetch)
     wk = sum(write) / len(write)
@@ -54,6 +61,7 @@ def main():
         "kernel": a.kernel,
         "kernel_hash": kernel_hash(),
         "launches_averaged": len(fetch),
+        "launches_per_round": a.per_round,
         "bench_args": a.bench_args,
         "fetch_size_kib_raw": fk,
         "write_size_kib_raw": wk,

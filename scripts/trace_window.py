@@ -37,10 +37,16 @@ def main():
     ap.add_argument("--marker", default="", help="family mode: the kernel whose dispatches end the rounds")
     ap.add_argument("--rounds", default="", help="family mode: first,last round (0-based, of the marker's count)")
     ap.add_argument("--bench-args", default="")
+    ap.add_argument("--per-round", type=int, default=1,
+                    help="launches of the kernel per round (2 with the round split on: the groups' launches "
+                         "overlap, so a round's time is taken from the end of the previous round's last launch "
+                         "to the end of its own; --first / --count then count rounds)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     if a.family:
         return family_mode(a)
+    if a.per_round > 1:
+        return split_mode(a)
     rows = []
     with open(a.csv) as f:
         for r in csv.DictReader(f):
@@ -57,6 +63,37 @@ def main():
            "avg_us": sum(us) / len(us), "min_us": min(us), "max_us": max(us),
            "durations_us": [round(x, 2) for x in us],
            "source": "rocprofv3 --kernel-trace (Start/End_Timestamp, ns)"}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps({k: v for k, v in out.items() if k != "durations_us"}))
+
+
+def split_mode(a):
+    """Rounds of --per-round overlapping launches (the round split): the time of round r is the
+    end of its last launch minus the end of round r - 1's last launch (the first round of the
+    run: minus its own first start), so the window's sum is the span the rounds took."""
+    rows = []
+    with open(a.csv) as f:
+        for r in csv.DictReader(f):
+            if a.kernel in r["Kernel_Name"]:
+                rows.append((int(r["Dispatch_Id"]), int(r["Start_Timestamp"]), int(r["End_Timestamp"]),
+                             r["Kernel_Name"]))
+    rows.sort()
+    n = a.per_round
+    rounds = [rows[i * n:(i + 1) * n] for i in range(len(rows) // n)]
+    if len(rounds) < a.first + a.count:
+        raise SystemExit(f"{len(rounds)} rounds of {a.kernel}; window [{a.first}, {a.first + a.count}) incomplete")
+    ends = [max(e for _, _, e, _ in rd) for rd in rounds]
+    us = []
+    for r in range(a.first, a.first + a.count):
+        t0 = ends[r - 1] if r else min(s for _, s, _, _ in rounds[0])
+        us.append((ends[r] - t0) / 1e3)
+    out = {"kernel": rows[0][3][:120], "kernel_hash": kernel_hash(), "bench_args": a.bench_args,
+           "launches_in_run": len(rows), "launches_per_round": n, "window_rounds": [a.first, a.first + a.count],
+           "avg_us": sum(us) / len(us), "min_us": min(us), "max_us": max(us),
+           "durations_us": [round(x, 2) for x in us],
+           "source": "rocprofv3 --kernel-trace (Start/End_Timestamp, ns); per round: end of the last launch minus "
+                     "the end of the previous round's"}
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
     print(json.dumps({k: v for k, v in out.items() if k != "durations_us"}))
