@@ -148,6 +148,16 @@ EXPORTS = {
     "gs_read_cluster_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "gs_read_cluster_rounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gs_run_simulations_cluster_tables": (C.c_int, [C.POINTER(SimConfig), C.c_void_p, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(C.c_void_p)]),
+    "gs_cluster_enable_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_cluster_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),
+    "gs_read_cluster_load_group": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_read_cluster_rounds_group": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_size_t)]),
     "gs_destroy": (None, [C.c_void_p]),
     "gs_set_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "gs_set_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -588,28 +598,58 @@ class Engine:
         return e, i, p, st, hh
 
     # --- cluster load view (per-node load summed over every slot) --------------
-    def enable_cluster_view(self, on=True):
+    def enable_cluster_view(self, on=True, groups=None, weights=None):
         """Allocates (or, on=False, frees) the cluster load view: from now on every recorded round
-        also sums the slots' egress / ingress / prunes / deliveries per node on the device."""
-        _check(lib().gs_cluster_enable(self.h, 1 if on else 0))
+        also sums the slots' egress / ingress / prunes / deliveries per node on the device.
+        groups: slot counts of consecutive slot groups (they sum to n_slots), or "tables" for one
+        group per trajectory table; weights: a u32 per slot (0 excludes the slot; default 1). With
+        either, every group keeps its own totals, peaks and rounds (cluster_load(group) ...)."""
+        if not on:
+            if groups is not None or weights is not None:
+                raise ValueError("enable_cluster_view: groups / weights go with on=True")
+            _check(lib().gs_cluster_enable(self.h, 0))
+            return
+        if groups is None and weights is None:
+            _check(lib().gs_cluster_enable(self.h, 1))
+            return
+        g, w = cluster_group_args(self.n_slots, groups, weights)
+        _check(lib().gs_cluster_enable_groups(self.h, None if g is None else _ptr(g), 0 if g is None else len(g),
+                                              None if w is None else _ptr(w)))
 
-    def cluster_load(self):
+    def cluster_groups(self):
+        """(slot counts of the enabled view's groups, the slots' weights): both u32 arrays."""
+        g = np.zeros(self.n_slots, dtype=np.uint32)  # (at most a group per slot)
+        w = np.zeros(self.n_slots, dtype=np.uint32)
+        cnt = C.c_uint32()
+        _check(lib().gs_cluster_groups(self.h, _ptr(g), len(g), C.byref(cnt), _ptr(w)))
+        return g[:cnt.value].copy(), w
+
+    def cluster_load(self, group=None):
         """Totals over the recorded rounds since set_slots -- egress, ingress, prunes, delivered,
-        hop_sum (u64 [n]) -- and the per-round peaks egress_peak, ingress_peak (u32 [n])."""
+        hop_sum (u64 [n]) -- and the per-round peaks egress_peak, ingress_peak (u32 [n]); of slot
+        group `group` of a grouped view (None: the only group)."""
         out = {k: np.zeros(self.n, dtype=np.uint64) for k in CLUSTER_TOTALS}
         out["egress_peak"] = np.zeros(self.n, dtype=np.uint32)
         out["ingress_peak"] = np.zeros(self.n, dtype=np.uint32)
-        _check(lib().gs_read_cluster_load(self.h, *[_ptr(out[k]) for k in CLUSTER_TOTALS], _ptr(out["egress_peak"]),
-                                          _ptr(out["ingress_peak"])))
+        ptrs = [_ptr(out[k]) for k in CLUSTER_TOTALS] + [_ptr(out["egress_peak"]), _ptr(out["ingress_peak"])]
+        if group is None:
+            _check(lib().gs_read_cluster_load(self.h, *ptrs))
+        else:
+            _check(lib().gs_read_cluster_load_group(self.h, _group_index(group), *ptrs))
         return out
 
-    def cluster_rounds(self):
-        """One CLUSTER_ROUND_DTYPE record per recorded round (row r of summaries() is the same round)."""
+    def cluster_rounds(self, group=None):
+        """One CLUSTER_ROUND_DTYPE record per recorded round (row r of summaries() is the same
+        round); of slot group `group` of a grouped view (None: the only group)."""
         cap = 1 << 12
+        g = None if group is None else _group_index(group)
         while True:
             out = np.zeros(cap, dtype=CLUSTER_ROUND_DTYPE)
             cnt = C.c_size_t()
-            rc = lib().gs_read_cluster_rounds(self.h, _ptr(out), cap, C.byref(cnt))
+            if g is None:
+                rc = lib().gs_read_cluster_rounds(self.h, _ptr(out), cap, C.byref(cnt))
+            else:
+                rc = lib().gs_read_cluster_rounds_group(self.h, g, _ptr(out), cap, C.byref(cnt))
             if rc == -4 and cnt.value > cap:
                 cap = cnt.value
                 continue
@@ -628,6 +668,43 @@ class Engine:
 
     def kernel_time_reset(self):
         _check(lib().gs_kernel_time_reset(self.h))
+
+
+def _group_index(group):
+    g = int(group)
+    if g < 0 or g != group:
+        raise ValueError(f"cluster view: group must be a non-negative integer, not {group!r}")
+    return g
+
+
+def _u32_array(what, x):
+    a = np.asarray(x)
+    if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF)):
+        raise ValueError(f"{what} must be a list of integers within [0, 2^32)")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def cluster_group_args(n_slots, groups, weights):
+    """Checks enable_cluster_view's groups / weights for an engine of n_slots slots (no device
+    needed) and returns them as u32 arrays (groups None for "tables" or when only weights are
+    given: one group per trajectory table; weights None for unit weights)."""
+    g = w = None
+    if groups is not None and not (isinstance(groups, str) and groups == "tables"):
+        if isinstance(groups, str):
+            raise ValueError(f'cluster view: groups is a list of slot counts or "tables", not {groups!r}')
+        g = _u32_array("cluster view: groups", groups)
+        if len(g) == 0 or len(g) > n_slots:
+            raise ValueError(f"cluster view: {len(g)} groups for {n_slots} slots")
+        if (g == 0).any():
+            raise ValueError(f"cluster view: group {int(np.argmax(g == 0))} is empty")
+        if int(g.astype(np.uint64).sum()) != n_slots:
+            raise ValueError(f"cluster view: groups sum to {int(g.astype(np.uint64).sum())}, the engine has "
+                             f"{n_slots} slots")
+    if weights is not None:
+        w = _u32_array("cluster view: weights", weights)
+        if w.shape != (n_slots,):
+            raise ValueError(f"cluster view: weights needs exactly n_slots = {n_slots} values")
+    return g, w
 
 
 class HopsStatOut(C.Structure):
@@ -677,7 +754,7 @@ def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, th
                     fanout=6, asz=12, iterations=1, warm_up=200, p=0.013333, thr=0.15, min_ingress_nodes=2,
                     fraction_to_fail=0.1, when_to_fail=0, nb_stranded=10, nb_message=5, nb_hops=15, test_type=0,
                     seed=0, device=0, bfs_mode=GS_BFS_AUTO, fanouts=None, aszs=None, rot_probs=None, seeds=None,
-                    cluster=False):
+                    cluster=False, cluster_weights=None):
     """gossip_main.rs run_simulation for n_sims sims as slots of one engine.
     fanouts: a push fanout per sim (the engine's capacity is their maximum; `fanout` is unused then).
     aszs / rot_probs: an active-set size / rotation probability per sim (default `asz` / `p`); sims
@@ -686,7 +763,10 @@ def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, th
     probability, seed) triples, so seed replicas run as one engine, each sim equal to its own
     run_simulations(seed=...) call.
     cluster: run the engine with its cluster load view on; the result then also answers
-    u64(sim, name) for CLUSTER_RESULT_NAMES (the same arrays under every sim)."""
+    u64(sim, name) for CLUSTER_RESULT_NAMES (the same arrays under every sim). cluster="tables":
+    the view is grouped by trajectory table -- the sims of one (size, probability, seed) -- and the
+    names under a sim answer with its own group's arrays; cluster_weights: a u32 weight per sim
+    (0 excludes the sim from its group's sums; "tables" only)."""
     st = np.ascontiguousarray(stakes, dtype=np.uint64)
     cfg = SimConfig(fanout, asz, iterations, warm_up, min_ingress_nodes, when_to_fail, p, thr, fraction_to_fail,
                     nb_stranded, nb_message, nb_hops, test_type, seed, device, bfs_mode)
@@ -706,8 +786,20 @@ def run_simulations(stakes, *, n_sims=1, origin_ranks=None, min_ingress=None, th
     sd = arr(seeds, np.uint64)
     if sd is not None and sd.shape != (n_sims,):
         raise ValueError(f"run_simulations: seeds needs exactly n_sims = {n_sims} values")
+    if isinstance(cluster, str) and cluster != "tables":
+        raise ValueError(f'run_simulations: cluster is True, False or "tables", not {cluster!r}')
+    by_table = isinstance(cluster, str)
+    if cluster_weights is not None and not by_table:
+        raise ValueError('run_simulations: cluster_weights needs cluster="tables"')
+    cw = None if cluster_weights is None else cluster_group_args(n_sims, None, cluster_weights)[1]
     h = C.c_void_p()
-    if cluster:
+    if by_table:
+        _check(lib().gs_run_simulations_cluster_tables(
+            C.byref(cfg), _ptr(st), len(st), n_sims, None if r is None else _ptr(r),
+            None if mi is None else _ptr(mi), None if th is None else _ptr(th), None if fr is None else _ptr(fr),
+            None if fo is None else _ptr(fo), None if az is None else _ptr(az), None if rp is None else _ptr(rp),
+            None if sd is None else _ptr(sd), None if cw is None else _ptr(cw), C.byref(h)))
+    elif cluster:
         _check(lib().gs_run_simulations_cluster(C.byref(cfg), _ptr(st), len(st), n_sims,
                                                 None if r is None else _ptr(r), None if mi is None else _ptr(mi),
                                                 None if th is None else _ptr(th), None if fr is None else _ptr(fr),

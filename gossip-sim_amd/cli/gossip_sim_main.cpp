@@ -20,7 +20,8 @@
 // network (--synthetic N) instead of an RPC pull; --influx other than `n` is refused.
 // --save-results / --replay-results keep the named result arrays of a run in a text
 // file and print the report from it again without a GPU. --cluster-load PATH runs every
-// engine with its cluster load view on and writes each node's load summed over all origins.
+// engine with its cluster load view on and writes each node's load summed over all origins;
+// --cluster-load-by-config PATH groups the view by trajectory table and writes it per table.
 #include <algorithm>
 #include <cerrno>
 #include <cinttypes>
@@ -30,6 +31,7 @@
 #include <string>
 #include <chrono>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/gossip_hip.h"
@@ -51,6 +53,10 @@ const char* U64_NAMES[] = {"origin", "hop_max", "hop_min", "aggregate_hops", "ld
 // per-round lines are not, and are not kept)
 const char* CLUSTER_NAMES[] = {"cluster_egress", "cluster_ingress", "cluster_prunes", "cluster_delivered",
                                "cluster_hop_sum"};
+
+// --cluster-load-by-config: the totals of one table's group are kept under the table's first
+// simulation, with the table's index within its engine under this name
+const char* CLUSTER_TABLE = "cluster_table";
 
 [[noreturn]] void die(int code, const std::string& msg) {
   std::fprintf(stderr, "error: %s\n", msg.c_str());
@@ -82,6 +88,7 @@ struct Cli {
   uint64_t synthetic = 0, seed = 0x5EED0003ull, gpus = 1, bfs_mode = GS_BFS_AUTO;
   std::string save_results, replay_results, engine_plan;
   std::string cluster_load;   // per-node load summed over every simulation of every engine
+  std::string cluster_by_config;  // per-node load per (engine, trajectory table)
   std::string influx_file;  // offline Influx line protocol (gs_influx.cpp)
   uint64_t influx_time_base = 0;
   bool batch_sweeps = false;  // an active-set-size / rotate-probability / push-fanout sweep as one engine per device
@@ -110,6 +117,11 @@ void usage() {
       "                       pubkey,stake,egress,ingress,prunes,delivered,hop_sum -- the measured rounds' totals\n"
       "                       summed over every simulation (origin) of every engine of the run; --save-results then\n"
       "                       keeps these totals, and --replay-results with --cluster-load rewrites the file\n"
+      "  --cluster-load-by-config PATH  run every engine with its view grouped by trajectory table (the simulations\n"
+      "                       of one active-set size, rotation probability and seed; one table per engine without\n"
+      "                       --batch-sweeps) and write one line per engine of the plan, table and node:\n"
+      "                       engine,table,pubkey,stake,egress,ingress,prunes,delivered,hop_sum -- --save-results keeps\n"
+      "                       each table's totals under its first simulation, and --replay-results rewrites the file\n"
       "  --engine-plan PATH   write one line per engine: device, simulations, active-set size, fanouts\n"
       "  --batch-sweeps       run an active-set-size, rotate-probability or push-fanout sweep as ONE engine per\n"
       "                       device (an active-set table per value) instead of one engine per value; a plan\n"
@@ -193,6 +205,7 @@ Cli parse(int argc, char** argv) {
     else if (a == "--replay-results") c.replay_results = need(i);
     else if (a == "--engine-plan") c.engine_plan = need(i);
     else if (a == "--cluster-load") c.cluster_load = need(i);
+    else if (a == "--cluster-load-by-config") c.cluster_by_config = need(i);
     else if (a == "--influx-file") c.influx_file = need(i);
     else if (a == "--influx-time-base") u64(i, c.influx_time_base);
     else if (a == "--batch-sweeps") c.batch_sweeps = true;
@@ -249,12 +262,18 @@ struct Job {
 };
 
 void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsrep::SimArrays>& out,
-             std::string& err, bool cluster) {
+             std::string& err, int cluster /*0 no view, 1 over the engine, 2 per trajectory table*/) {
   gs_sim_config cfg = j.cfg;
   cfg.device = j.device;
   gs_sim_result* r = nullptr;
   const int rc =
-      cluster ? gs_run_simulations_cluster(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+      cluster == 2
+          ? gs_run_simulations_cluster_tables(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
+                                              j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(),
+                                              j.slot_fanouts || j.traj ? j.fanouts.data() : nullptr,
+                                              j.traj ? j.aszs.data() : nullptr, j.traj ? j.probs.data() : nullptr,
+                                              j.traj && !j.seeds.empty() ? j.seeds.data() : nullptr, nullptr, &r)
+      : cluster ? gs_run_simulations_cluster(&cfg, stakes.data(), (uint32_t)stakes.size(), (uint32_t)j.sims.size(),
                                            j.ranks.data(), j.mi.data(), j.thr.data(), j.frac.data(),
                                            j.slot_fanouts || j.traj ? j.fanouts.data() : nullptr,
                                            j.traj ? j.aszs.data() : nullptr, j.traj ? j.probs.data() : nullptr,
@@ -273,8 +292,20 @@ void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsre
     err = std::string("gs_run_simulations: ") + gs_last_error();
     return;
   }
+  // (per table: the engine's tables stand in the order of their first simulation, gs_traj_plan.h)
+  std::vector<std::tuple<uint32_t, double, uint64_t>> tabs;
   for (size_t k = 0; k < j.sims.size(); ++k) {
     gsrep::SimArrays& a = out[j.sims[k]];
+    bool first_of_table = false;
+    if (cluster == 2) {
+      const auto key = j.traj ? std::make_tuple(j.aszs[k], j.probs[k], j.seeds.empty() ? (uint64_t)0 : j.seeds[k])
+                              : std::make_tuple((uint32_t)0, 0.0, (uint64_t)0);
+      first_of_table = std::find(tabs.begin(), tabs.end(), key) == tabs.end();
+      if (first_of_table) {
+        a.u[CLUSTER_TABLE] = {(uint64_t)tabs.size()};
+        tabs.push_back(key);
+      }
+    }
     for (const char* nm : F64_NAMES) {
       const size_t n = gs_result_f64(r, (uint32_t)k, nm, nullptr, 0);
       if (n == SIZE_MAX) continue;
@@ -287,12 +318,13 @@ void run_job(const Job& j, const std::vector<uint64_t>& stakes, std::vector<gsre
       a.u[nm].resize(n);
       gs_result_u64(r, (uint32_t)k, nm, a.u[nm].data(), n);
     }
-    if (cluster && k == 0)  // the engine's totals once, under its first simulation
+    // the engine's totals once, under its first simulation; per table: the table's, under its first
+    if (cluster == 2 ? first_of_table : cluster && k == 0)
       for (const char* nm : CLUSTER_NAMES) {
-        const size_t n = gs_result_u64(r, 0, nm, nullptr, 0);
+        const size_t n = gs_result_u64(r, (uint32_t)k, nm, nullptr, 0);
         if (n == SIZE_MAX) continue;
         a.u[nm].resize(n);
-        gs_result_u64(r, 0, nm, a.u[nm].data(), n);
+        gs_result_u64(r, (uint32_t)k, nm, a.u[nm].data(), n);
       }
   }
   gs_result_free(r);
@@ -591,7 +623,7 @@ int main(int argc, char** argv) {
           if ((uint64_t)j.device != d || !errs[d].empty()) continue;
           Job jj = j;
           jj.device = ndev > 0 ? (int)(d % (uint64_t)ndev) : 0;
-          run_job(jj, stakes, sims, errs[d], !c.cluster_load.empty());
+          run_job(jj, stakes, sims, errs[d], !c.cluster_by_config.empty() ? 2 : !c.cluster_load.empty() ? 1 : 0);
         }
       });
     for (auto& t : th) t.join();
@@ -627,6 +659,39 @@ int main(int argc, char** argv) {
     for (size_t v = 0; v < nn; ++v)
       std::fprintf(f, "%s,%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 "\n", keys[v].c_str(),
                    stakes[v], tot[0][v], tot[1][v], tot[2][v], tot[3][v], tot[4][v]);
+    std::fclose(f);
+  }
+  if (!c.cluster_by_config.empty()) {  // one block of lines per (engine of the plan, table), in plan order
+    const size_t nn = stakes.size();
+    bool any = false;
+    for (const Job& j : jobs)
+      for (size_t i : j.sims) any = any || (i < sims.size() && sims[i].u.count(CLUSTER_TABLE));
+    if (!any && num_sims && !c.replay_results.empty())
+      die(1, c.replay_results + " holds no cluster_table totals (it was saved without --cluster-load-by-config)");
+    struct Block { size_t engine; uint64_t table; const std::vector<uint64_t>* tot[5]; };
+    std::vector<Block> blocks;  // (checked before the file is created)
+    for (size_t e = 0; e < jobs.size(); ++e)
+      for (size_t i : jobs[e].sims) {
+        if (i >= sims.size()) continue;
+        const auto tt = sims[i].u.find(CLUSTER_TABLE);
+        if (tt == sims[i].u.end() || tt->second.empty()) continue;
+        Block b{e, tt->second[0], {}};
+        for (size_t w = 0; w < 5; ++w) {
+          const auto it = sims[i].u.find(CLUSTER_NAMES[w]);
+          if (it == sims[i].u.end() || it->second.size() != nn)
+            die(1, std::string(CLUSTER_NAMES[w]) + " of simulation " + std::to_string(i) + " does not hold " +
+                       std::to_string(nn) + " nodes");
+          b.tot[w] = &it->second;
+        }
+        blocks.push_back(b);
+      }
+    FILE* f = std::fopen(c.cluster_by_config.c_str(), "w");
+    if (!f) die(1, "cannot write " + c.cluster_by_config);
+    for (const Block& b : blocks)
+      for (size_t v = 0; v < nn; ++v)
+        std::fprintf(f, "%zu,%" PRIu64 ",%s,%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 "\n",
+                     b.engine, b.table, keys[v].c_str(), stakes[v], (*b.tot[0])[v], (*b.tot[1])[v], (*b.tot[2])[v],
+                     (*b.tot[3])[v], (*b.tot[4])[v]);
     std::fclose(f);
   }
   if (!c.influx_file.empty()) {  // the datapoint queue's text, in enqueue order (gossip_main.rs:372-645)

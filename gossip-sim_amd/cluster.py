@@ -14,6 +14,25 @@ def stake_bucket(stake):
     return min(int(int(stake) // LAMPORTS_PER_SOL).bit_length(), NUM_BUCKETS - 1)
 
 
+def stake_weights(stakes, origins, scale=1000):
+    """Integer weights for a grouped view's slots (Engine.enable_cluster_view(weights=...)) from
+    the origins' stakes: max(1, stake * scale // max stake), the largest stake of the WHOLE
+    network, in Python integers (no rounding: stake * scale may pass 2^64). So the max-stake node
+    weighs `scale`, equal stakes weigh the same and a tiny stake still counts once. u32 [len(origins)]."""
+    st = [int(s) for s in np.asarray(stakes, dtype=np.uint64).tolist()]
+    scale = int(scale)
+    if not st or scale < 1 or scale > 0xFFFFFFFF:
+        raise ValueError("stake_weights: needs a network and 1 <= scale < 2^32")
+    top = max(st)
+    out = []
+    for o in origins:
+        o = int(o)
+        if o < 0 or o >= len(st):
+            raise ValueError(f"stake_weights: origin {o} is no node of the network ({len(st)})")
+        out.append(max(1, st[o] * scale // top) if top else 1)
+    return np.array(out, dtype=np.uint32)
+
+
 def _spread(a):
     """min / median / p99 / max of a per-node array; the p99 is the value of rank
     ceil(0.99 n) in ascending order (an element of the array, no interpolation)."""

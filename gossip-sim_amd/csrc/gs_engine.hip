@@ -1152,11 +1152,11 @@ static int drain_summaries(Engine* e) {
   e->h_sum.resize(old + n);
   HIPC(hipMemcpyAsync(e->h_sum.data() + old, e->sum, n * sizeof(gs_round_summary), hipMemcpyDeviceToHost, e->st));
   if (e->cl_on) {  // the cluster view's entries of the same rounds (index r stays the same round in both)
-    const size_t co = e->h_cl.size();
-    e->h_cl.resize(co + e->sum_used);
-    HIPC(hipMemcpyAsync(e->h_cl.data() + co, e->cl_ring, e->sum_used * sizeof(gs_cluster_round), hipMemcpyDeviceToHost,
+    const size_t co = e->h_cl.size(), ne = (size_t)e->sum_used * e->cl_G;  // (G entries per round, [round][G])
+    e->h_cl.resize(co + ne);
+    HIPC(hipMemcpyAsync(e->h_cl.data() + co, e->cl_ring, ne * sizeof(gs_cluster_round), hipMemcpyDeviceToHost,
                         e->st));
-    HIPC(hipMemsetAsync(e->cl_ring, 0, e->sum_used * sizeof(gs_cluster_round), e->st));
+    HIPC(hipMemsetAsync(e->cl_ring, 0, ne * sizeof(gs_cluster_round), e->st));
     HIPC(hipStreamSynchronize(e->st));
     for (size_t i = co; i < e->h_cl.size(); ++i) {  // k_cluster_fold's keys: max << 32 | ~node
       gs_cluster_round& c = e->h_cl[i];
@@ -1704,20 +1704,40 @@ int gs_read_accumulators(gs_engine* eh, uint32_t slot, uint64_t* egress, uint64_
 // ------------------------------------------------- cluster load view ----
 static int cluster_zero(Engine* e) {
   if (!e->cl_on) return GS_OK;
-  HIPC(hipMemsetAsync(e->cl_scr, 0, (size_t)5 * e->NP * 4, e->st));
-  HIPC(hipMemsetAsync(e->cl_tot, 0, (size_t)5 * e->NP * 8, e->st));
-  HIPC(hipMemsetAsync(e->cl_peak, 0, (size_t)2 * e->NP * 4, e->st));
-  HIPC(hipMemsetAsync(e->cl_ring, 0, (size_t)e->sum_cap * sizeof(gs_cluster_round), e->st));
+  const size_t G = e->cl_G;
+  HIPC(hipMemsetAsync(e->cl_scr, 0, G * 5 * e->NP * 4, e->st));
+  HIPC(hipMemsetAsync(e->cl_tot, 0, G * 5 * e->NP * 8, e->st));
+  HIPC(hipMemsetAsync(e->cl_peak, 0, G * 2 * e->NP * 4, e->st));
+  HIPC(hipMemsetAsync(e->cl_ring, 0, G * e->sum_cap * sizeof(gs_cluster_round), e->st));
   return GS_OK;
 }
 
 static void cluster_free(Engine* e) {
-  dfree(*e, e->cl_scr, (size_t)5 * e->NP);
-  dfree(*e, e->cl_tot, (size_t)5 * e->NP);
-  dfree(*e, e->cl_peak, (size_t)2 * e->NP);
-  dfree(*e, e->cl_ring, (size_t)e->sum_cap);
+  const size_t G = e->cl_G;
+  dfree(*e, e->cl_scr, G * 5 * e->NP);
+  dfree(*e, e->cl_tot, G * 5 * e->NP);
+  dfree(*e, e->cl_peak, G * 2 * e->NP);
+  dfree(*e, e->cl_ring, G * e->sum_cap);
+  dfree(*e, e->cl_chunks, std::max<size_t>(2, e->cl_nchunks));  // (at least 16 B each: dalloc and dfree
+  dfree(*e, e->cl_wts, std::max<size_t>(4, e->S));              //  count smaller blocks differently)
   e->cl_on = false;
+  e->cl_grouped = false;
+  e->cl_G = 1;
+  e->cl_nchunks = 0;
+  e->cl_gsz.clear();
+  e->cl_w.clear();
   e->h_cl.clear();
+}
+
+// the enabled view's grouping as (sizes, weights): one group of unit weights for gs_cluster_enable's
+static void cluster_grouping(const Engine* e, std::vector<uint32_t>& gsz, std::vector<uint32_t>& w) {
+  if (e->cl_grouped) {
+    gsz = e->cl_gsz;
+    w = e->cl_w;
+  } else {
+    gsz.assign(1, e->S);
+    w.assign(e->S, 1u);
+  }
 }
 
 int gs_cluster_enable(gs_engine* eh, int on) {
@@ -1731,7 +1751,12 @@ int gs_cluster_enable(gs_engine* eh, int on) {
     cluster_free(e);
     return GS_OK;
   }
-  if (e->cl_on) return GS_OK;
+  if (e->cl_on) {
+    if (e->cl_grouped && (e->cl_G != 1 || std::count(e->cl_w.begin(), e->cl_w.end(), 1u) != (ptrdiff_t)e->S))
+      return fail(GS_ESTATE, "gs_cluster_enable: a view with slot groups or weights is enabled (gs_cluster_enable_groups); "
+                             "disable it first");
+    return GS_OK;
+  }
   // a round's per-node sums stay in u32: egress bytes and hops <= 255, in-degrees <= the inbound capacity
   if ((uint64_t)e->S * std::max<uint64_t>(255, e->capin) >= (1ull << 32))
     return fail(GS_ERANGE, "gs_cluster_enable: n_slots x max(255, inbound capacity) must stay below 2^32");
@@ -1752,32 +1777,139 @@ int gs_cluster_enable(gs_engine* eh, int on) {
   return GS_OK;
 }
 
+int gs_cluster_enable_groups(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
+  ENGINE(eh);
+  if (e->part_on)
+    return fail(GS_ESTATE, "gs_cluster_enable_groups: a node-range partition rank holds its own nodes' pairs only (the "
+                           "partitioned view needs an exchange of the per-round sums)");
+  std::vector<uint32_t> gsz;
+  if (!group_slots) {
+    if (n_groups) return fail(GS_EINVAL, "gs_cluster_enable_groups: group_slots is null but n_groups is not 0");
+    for (const TrajTab& t : e->traj) gsz.push_back(t.ns);  // one group per trajectory table (gs_create: one)
+  } else {
+    if (n_groups == 0 || n_groups > e->S)
+      return fail(GS_EINVAL, "gs_cluster_enable_groups: n_groups must be within [1, n_slots]");
+    gsz.assign(group_slots, group_slots + n_groups);
+  }
+  uint64_t sum = 0;
+  for (size_t g = 0; g < gsz.size(); ++g) {
+    if (!gsz[g]) return fail(GS_EINVAL, "gs_cluster_enable_groups: group_slots[" + std::to_string(g) + "] is an empty group");
+    sum += gsz[g];
+  }
+  if (sum != e->S)
+    return fail(GS_EINVAL, "gs_cluster_enable_groups: group_slots sum to " + std::to_string(sum) + ", the engine has " +
+                               std::to_string(e->S) + " slots");
+  std::vector<uint32_t> w(e->S, 1u);
+  if (weights) w.assign(weights, weights + e->S);
+  if (e->cl_on) {  // the identical grouping again is a no-op; another one needs a disable first
+    std::vector<uint32_t> g0, w0;
+    cluster_grouping(e, g0, w0);
+    if (g0 == gsz && w0 == w) return GS_OK;
+    return fail(GS_ESTATE, "gs_cluster_enable_groups: a view with another grouping or other weights is enabled; "
+                           "disable it first (gs_cluster_enable(e, 0))");
+  }
+  // a round's per-node sums of a group stay in u32 (gs_cluster_enable's rule with the slots' weights)
+  const uint64_t top = std::max<uint64_t>(255, e->capin);
+  for (size_t g = 0, a = 0; g < gsz.size(); a += gsz[g], ++g) {
+    uint64_t ws = 0;
+    for (uint32_t j = 0; j < gsz[g]; ++j) ws += w[a + j];
+    if (ws * top >= (1ull << 32))  // (ws < 2^32 * n_slots: no overflow of the product's test below 2^64)
+      return fail(GS_ERANGE, "gs_cluster_enable_groups: group " + std::to_string(g) + ": (sum of weights " +
+                                 std::to_string(ws) + ") x max(255, inbound capacity) must stay below 2^32");
+  }
+  const uint32_t G = (uint32_t)gsz.size();
+  const std::vector<ClusterChunk> plan = cluster_plan_build(e->NP, gsz.data(), G);
+  if (G > 65535 || plan.size() > 65535)
+    return fail(GS_ERANGE, "gs_cluster_enable_groups: more than 65,535 groups or slot chunks (a launch's grid limit)");
+  if (int s = drain_summaries(e)) return s;  // (the ring rows before now belong to rounds without the view)
+  e->cl_G = G;  // (cluster_free counts with it)
+  e->cl_nchunks = (uint32_t)plan.size();
+  int s = dalloc(*e, &e->cl_scr, (size_t)G * 5 * e->NP, 0);
+  if (!s) s = dalloc(*e, &e->cl_tot, (size_t)G * 5 * e->NP, 0);
+  if (!s) s = dalloc(*e, &e->cl_peak, (size_t)G * 2 * e->NP, 0);
+  if (!s) s = dalloc(*e, &e->cl_ring, (size_t)G * e->sum_cap, 0);
+  if (!s) s = dalloc(*e, &e->cl_chunks, std::max<size_t>(2, plan.size()), 0);
+  if (!s) s = dalloc(*e, &e->cl_wts, std::max<size_t>(4, e->S), 0);
+  if (!s) {
+    hipError_t r = hipMemcpyAsync(e->cl_chunks, plan.data(), plan.size() * sizeof(ClusterChunk), hipMemcpyHostToDevice, e->st);
+    if (r == hipSuccess) r = hipMemcpyAsync(e->cl_wts, w.data(), (size_t)e->S * 4, hipMemcpyHostToDevice, e->st);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->st);  // (plan and w are locals)
+    if (r != hipSuccess) s = fail(GS_EHIP, std::string("gs_cluster_enable_groups: ") + hipGetErrorString(r));
+  }
+  if (s) {  // all or none
+    const std::string msg = g_err;
+    hipStreamSynchronize(e->st);
+    cluster_free(e);
+    return fail(s, msg);
+  }
+  e->cl_on = true;
+  e->cl_grouped = true;
+  e->cl_gsz = gsz;
+  e->cl_w = w;
+  e->h_cl.assign(e->h_sum.size() / e->S * G, gs_cluster_round{});
+  return GS_OK;
+}
+
+int gs_cluster_groups(gs_engine* eh, uint32_t* group_slots, uint32_t cap, uint32_t* n_groups, uint32_t* weights) {
+  ENGINE(eh);
+  if (!e->cl_on) return fail(GS_ESTATE, "the cluster load view is not enabled (gs_cluster_enable)");
+  if (!n_groups) return fail(GS_EINVAL, "gs_cluster_groups: n_groups is null");
+  std::vector<uint32_t> gsz, w;
+  cluster_grouping(e, gsz, w);
+  *n_groups = (uint32_t)gsz.size();
+  if (gsz.size() > cap) return fail(GS_ERANGE, "gs_cluster_groups: group buffer too small");
+  if (!group_slots) return fail(GS_EINVAL, "gs_cluster_groups: group_slots is null");
+  std::copy(gsz.begin(), gsz.end(), group_slots);
+  if (weights) std::copy(w.begin(), w.end(), weights);
+  return GS_OK;
+}
+
+int gs_read_cluster_load_group(gs_engine* eh, uint32_t g, uint64_t* egress, uint64_t* ingress, uint64_t* prunes,
+                               uint64_t* delivered, uint64_t* hop_sum, uint32_t* egress_peak, uint32_t* ingress_peak) {
+  ENGINE(eh);
+  if (!e->cl_on) return fail(GS_ESTATE, "the cluster load view is not enabled (gs_cluster_enable)");
+  if (g >= e->cl_G) return fail(GS_EINVAL, "group out of range");
+  if (int s = check_err(e)) return s;
+  const size_t N = e->NP;
+  const uint64_t* gt = e->cl_tot + (size_t)g * 5 * N;
+  const uint32_t* gp = e->cl_peak + (size_t)g * 2 * N;
+  uint64_t* tot[5] = {egress, ingress, prunes, delivered, hop_sum};
+  for (int w = 0; w < 5; ++w)
+    if (tot[w]) HIPC(hipMemcpyAsync(tot[w], gt + w * N, N * 8, hipMemcpyDeviceToHost, e->st));
+  if (egress_peak) HIPC(hipMemcpyAsync(egress_peak, gp, N * 4, hipMemcpyDeviceToHost, e->st));
+  if (ingress_peak) HIPC(hipMemcpyAsync(ingress_peak, gp + N, N * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  return GS_OK;
+}
+
 int gs_read_cluster_load(gs_engine* eh, uint64_t* egress, uint64_t* ingress, uint64_t* prunes, uint64_t* delivered,
                          uint64_t* hop_sum, uint32_t* egress_peak, uint32_t* ingress_peak) {
   ENGINE(eh);
   if (!e->cl_on) return fail(GS_ESTATE, "the cluster load view is not enabled (gs_cluster_enable)");
+  if (e->cl_G > 1) return fail(GS_EINVAL, "the view has several groups: read one with gs_read_cluster_load_group");
+  return gs_read_cluster_load_group(eh, 0, egress, ingress, prunes, delivered, hop_sum, egress_peak, ingress_peak);
+}
+
+int gs_read_cluster_rounds_group(gs_engine* eh, uint32_t g, gs_cluster_round* out, size_t cap, size_t* count) {
+  ENGINE(eh);
+  if (!e->cl_on) return fail(GS_ESTATE, "the cluster load view is not enabled (gs_cluster_enable)");
+  if (g >= e->cl_G) return fail(GS_EINVAL, "group out of range");
+  if (!count) return fail(GS_EINVAL, "null argument");
   if (int s = check_err(e)) return s;
-  const size_t N = e->NP;
-  uint64_t* tot[5] = {egress, ingress, prunes, delivered, hop_sum};
-  for (int w = 0; w < 5; ++w)
-    if (tot[w]) HIPC(hipMemcpyAsync(tot[w], e->cl_tot + w * N, N * 8, hipMemcpyDeviceToHost, e->st));
-  if (egress_peak) HIPC(hipMemcpyAsync(egress_peak, e->cl_peak, N * 4, hipMemcpyDeviceToHost, e->st));
-  if (ingress_peak) HIPC(hipMemcpyAsync(ingress_peak, e->cl_peak + N, N * 4, hipMemcpyDeviceToHost, e->st));
-  HIPC(hipStreamSynchronize(e->st));
+  if (int s = drain_summaries(e)) return s;
+  const size_t G = e->cl_G, n = e->h_cl.size() / G;
+  *count = n;
+  if (n > cap) return fail(GS_ERANGE, "cluster round buffer too small");
+  if (n && !out) return fail(GS_EINVAL, "null argument");
+  for (size_t r = 0; r < n; ++r) out[r] = e->h_cl[r * G + g];
   return GS_OK;
 }
 
 int gs_read_cluster_rounds(gs_engine* eh, gs_cluster_round* out, size_t cap, size_t* count) {
   ENGINE(eh);
   if (!e->cl_on) return fail(GS_ESTATE, "the cluster load view is not enabled (gs_cluster_enable)");
-  if (!count) return fail(GS_EINVAL, "null argument");
-  if (int s = check_err(e)) return s;
-  if (int s = drain_summaries(e)) return s;
-  *count = e->h_cl.size();
-  if (e->h_cl.size() > cap) return fail(GS_ERANGE, "cluster round buffer too small");
-  if (e->h_cl.size() && !out) return fail(GS_EINVAL, "null argument");
-  if (!e->h_cl.empty()) std::memcpy(out, e->h_cl.data(), e->h_cl.size() * sizeof(gs_cluster_round));
-  return GS_OK;
+  if (e->cl_G > 1) return fail(GS_EINVAL, "the view has several groups: read one with gs_read_cluster_rounds_group");
+  return gs_read_cluster_rounds_group(eh, 0, out, cap, count);
 }
 
 int gs_read_failed(gs_engine* eh, uint32_t slot, uint8_t* failed) {

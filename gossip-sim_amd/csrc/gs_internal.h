@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/gossip_hip.h"
+#include "gs_cluster_plan.h"
 #include "gs_mv_groups.h"
 #include "gs_split_plan.h"
 
@@ -283,6 +284,16 @@ struct Engine {
   uint32_t* cl_peak = nullptr;         // [2][NP] largest egress / ingress of one recorded round
   gs_cluster_round* cl_ring = nullptr; // [sum_cap] entry r belongs to summaries ring row r (raw keys: k_cluster_fold)
   std::vector<gs_cluster_round> h_cl;  // drained entries (index = recorded round, like h_sum)
+  // grouped view (gs_cluster_enable_groups): cl_G groups of consecutive slots and a weight per slot.
+  // The arrays above are then [G][5][NP], [G][5][NP], [G][2][NP] and [sum_cap][G], h_cl is
+  // [round][G], and launch_cluster_view runs the grouped kernels over the chunk table.
+  bool cl_grouped = false;
+  uint32_t cl_G = 1;
+  std::vector<uint32_t> cl_gsz;        // slots of each group (empty without a grouped view)
+  std::vector<uint32_t> cl_w;          // weight of each slot
+  ClusterChunk* cl_chunks = nullptr;   // [cl_nchunks] gs_cluster_plan.h
+  uint32_t cl_nchunks = 0;
+  uint32_t* cl_wts = nullptr;          // [S]
   uint32_t* err = nullptr;
   uint32_t* h_err = nullptr;  // pinned
   unsigned long long* phase_clk = nullptr;  // GS_PHASE_PROFILE=1: per-phase workgroup clock sums

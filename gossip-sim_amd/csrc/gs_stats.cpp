@@ -210,7 +210,7 @@ int gs_run_simulations(const gs_sim_config* cfg, const uint64_t* stakes, uint32_
 static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
                     const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                     const double* fractions, const uint32_t* fanouts, const gs_traj* traj, uint32_t n_traj,
-                    const uint64_t* tab_seeds, int cluster, gs_sim_result** out) {
+                    const uint64_t* tab_seeds, int cluster, const uint32_t* weights, gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
   gs_params prm{};
@@ -245,7 +245,8 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
 #define CK(x) do { r = (x); if (r) { gs_destroy(e); return r; } } while (0)
   CK(gs_set_slots(e, slots.data(), n_sims));
   if (fanouts) CK(gs_set_slot_fanouts(e, fanouts));
-  if (cluster) CK(gs_cluster_enable(e, 1));  // the cluster load view over every sim of the engine
+  if (cluster == 2) CK(gs_cluster_enable_groups(e, nullptr, 0, weights));  // a group per table, weights per sim
+  else if (cluster) CK(gs_cluster_enable(e, 1));  // the cluster load view over every sim of the engine
   CK(gs_init_active_sets(e));
   for (uint32_t it = 0; it < cfg->iterations; ++it) {
     if (cfg->test_type == 5 && it == cfg->when_to_fail) CK(gs_fail_nodes(e, frac.data()));
@@ -258,16 +259,27 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
   CK(gs_read_round_summaries(e, sums.data(), sums.size(), &nsum));
   std::unique_ptr<gs_sim_result> res(new gs_sim_result());  // released to *out only on success
   res->sims.resize(n_sims);
-  std::map<std::string, std::vector<uint64_t>> cl;  // the cluster view's arrays: the same under every sim
+  // the cluster view's arrays: the same under every sim of a group (cluster == 1: one group)
+  std::vector<std::map<std::string, std::vector<uint64_t>>> cls;
+  std::vector<uint32_t> sim_group(n_sims, 0);
+  uint32_t n_groups = 0;
   if (cluster) {
+    std::vector<uint32_t> gsz(n_sims);  // (at most a group per slot)
+    CK(gs_cluster_groups(e, gsz.data(), n_sims, &n_groups, nullptr));
+    for (uint32_t g = 0, a = 0; g < n_groups; a += gsz[g], ++g)
+      for (uint32_t j = 0; j < gsz[g]; ++j) sim_group[a + j] = g;
+    cls.resize(n_groups);
+  }
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    std::map<std::string, std::vector<uint64_t>>& cl = cls[g];
     std::vector<uint64_t> tot[5];
     for (auto& t : tot) t.resize(n);
     std::vector<uint32_t> pe(n), pi(n);
-    CK(gs_read_cluster_load(e, tot[0].data(), tot[1].data(), tot[2].data(), tot[3].data(), tot[4].data(), pe.data(),
-                            pi.data()));
+    CK(gs_read_cluster_load_group(e, g, tot[0].data(), tot[1].data(), tot[2].data(), tot[3].data(), tot[4].data(),
+                                  pe.data(), pi.data()));
     std::vector<gs_cluster_round> cr(rounds + 1);
     size_t ncr = 0;
-    CK(gs_read_cluster_rounds(e, cr.data(), cr.size(), &ncr));
+    CK(gs_read_cluster_rounds_group(e, g, cr.data(), cr.size(), &ncr));
     cl["cluster_egress"] = tot[0]; cl["cluster_ingress"] = tot[1]; cl["cluster_prunes"] = tot[2];
     cl["cluster_delivered"] = tot[3]; cl["cluster_hop_sum"] = tot[4];
     cl["cluster_egress_peak"].assign(pe.begin(), pe.end());
@@ -287,7 +299,8 @@ static int run_sims(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n
   std::vector<uint8_t> failed(n);
   for (uint32_t s = 0; s < n_sims; ++s) {
     SimStats& o = res->sims[s];
-    for (const auto& kv : cl) o.u[kv.first] = kv.second;
+    if (cluster)
+      for (const auto& kv : cls[sim_group[s]]) o.u[kv.first] = kv.second;
     CK(gs_read_accumulators(e, s, eg.data(), in.data(), pr.data(), st.data(), hh.data()));
     CK(gs_read_failed(e, s, failed.data()));
     std::vector<double> cov, rmr, br, hmean, hmed, smean, smed;
@@ -408,7 +421,7 @@ int gs_run_simulations_fanouts(const gs_sim_config* cfg, const uint64_t* stakes,
                                const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                                const double* fractions, const uint32_t* fanouts, gs_sim_result** out) {
   return run_sims(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, nullptr, 0,
-                  out);
+                  nullptr, out);
 }
 
 // A value of active-set size, rotation probability and (seeds != null) Philox seed per sim: the
@@ -418,7 +431,7 @@ static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, ui
                             const uint32_t* origin_ranks, const uint32_t* min_ingress, const double* thresholds,
                             const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
                             const double* rotation_probabilities, const uint64_t* seeds, int cluster,
-                            gs_sim_result** out) {
+                            const uint32_t* weights, gs_sim_result** out) {
   if (!cfg || !stakes || !out || n_sims == 0) return GS_EINVAL;
   *out = nullptr;
   const gs::TrajPlan pl = gs::traj_plan_build(n_sims, active_set_sizes, rotation_probabilities, seeds,
@@ -429,7 +442,7 @@ static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, ui
     c.rotation_probability = pl.tabs[0].p;
     c.seed = pl.tabs[0].seed;
     return run_sims(&c, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts, nullptr, 0, nullptr,
-                    cluster, out);
+                    cluster, weights, out);
   }
   std::vector<gs_traj> tabs;
   std::vector<uint64_t> tseeds;
@@ -438,7 +451,7 @@ static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, ui
     tseeds.push_back(t.seed);
   }
   const std::vector<uint32_t>& sim_of = pl.sim_of;
-  std::vector<uint32_t> orr(n_sims), mi(n_sims), fo(n_sims);
+  std::vector<uint32_t> orr(n_sims), mi(n_sims), fo(n_sims), wt(n_sims, 1u);
   std::vector<double> th(n_sims), fr(n_sims);
   for (uint32_t s = 0; s < n_sims; ++s) {
     const uint32_t i = sim_of[s];
@@ -447,10 +460,12 @@ static int run_sims_grouped(const gs_sim_config* cfg, const uint64_t* stakes, ui
     th[s] = thresholds ? thresholds[i] : cfg->prune_stake_threshold;
     fr[s] = fractions ? fractions[i] : cfg->fraction_to_fail;
     fo[s] = fanouts ? fanouts[i] : cfg->push_fanout;
+    if (weights) wt[s] = weights[i];
   }
   gs_sim_result* res = nullptr;
   const int r = run_sims(cfg, stakes, n, n_sims, orr.data(), mi.data(), th.data(), fr.data(), fanouts ? fo.data() : nullptr,
-                         tabs.data(), (uint32_t)tabs.size(), seeds ? tseeds.data() : nullptr, cluster, &res);
+                         tabs.data(), (uint32_t)tabs.size(), seeds ? tseeds.data() : nullptr, cluster,
+                         weights ? wt.data() : nullptr, &res);
   if (r) return r;
   std::vector<SimStats> by_sim(n_sims);
   for (uint32_t s = 0; s < n_sims; ++s) by_sim[sim_of[s]] = std::move(res->sims[s]);
@@ -467,7 +482,7 @@ int gs_run_simulations_traj(const gs_sim_config* cfg, const uint64_t* stakes, ui
     return gs_run_simulations_fanouts(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
                                       out);
   return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
-                          active_set_sizes, rotation_probabilities, nullptr, 0, out);
+                          active_set_sizes, rotation_probabilities, nullptr, 0, nullptr, out);
 }
 
 // ... and a Philox seed per sim (seeds == NULL: exactly gs_run_simulations_traj): the tables are
@@ -480,7 +495,7 @@ int gs_run_simulations_seeds(const gs_sim_config* cfg, const uint64_t* stakes, u
     return gs_run_simulations_traj(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
                                    active_set_sizes, rotation_probabilities, out);
   return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
-                          active_set_sizes, rotation_probabilities, seeds, 0, out);
+                          active_set_sizes, rotation_probabilities, seeds, 0, nullptr, out);
 }
 
 // ... and the cluster load view over the engine's sims (cluster == 0: exactly gs_run_simulations_seeds)
@@ -494,7 +509,18 @@ int gs_run_simulations_cluster(const gs_sim_config* cfg, const uint64_t* stakes,
                                     active_set_sizes, rotation_probabilities, seeds, out);
   // (the grouping handles one table and null per-sim arrays alike)
   return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
-                          active_set_sizes, rotation_probabilities, seeds, cluster, out);
+                          active_set_sizes, rotation_probabilities, seeds, 1, nullptr, out);
+}
+
+// ... with the view grouped by trajectory table (gs_cluster_enable_groups) and a weight per sim:
+// the cluster_* names under a sim answer with the arrays of that sim's own table's group
+int gs_run_simulations_cluster_tables(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n, uint32_t n_sims,
+                                      const uint32_t* origin_ranks, const uint32_t* min_ingress,
+                                      const double* thresholds, const double* fractions, const uint32_t* fanouts,
+                                      const uint32_t* active_set_sizes, const double* rotation_probabilities,
+                                      const uint64_t* seeds, const uint32_t* weights, gs_sim_result** out) {
+  return run_sims_grouped(cfg, stakes, n, n_sims, origin_ranks, min_ingress, thresholds, fractions, fanouts,
+                          active_set_sizes, rotation_probabilities, seeds, 2, weights, out);
 }
 
 }  // extern "C"

@@ -308,12 +308,16 @@ def traj_batchable_multi(cfgs, n_nodes):
                                 max(c.get("asz", 12) for c in cfgs))
 
 
-def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_device=None, runner=None, multi=False):
+def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_device=None, runner=None, multi=False,
+                   cluster=None):
     """run_sweep with each rank's share as ONE engine of several trajectory tables: the same
     arguments (values dealt round-robin over the ranks, make_cfg(value) -> kwargs of
     run_simulations) and bit-identical results. A share that cannot batch (traj_batchable)
     runs one engine per value, as run_sweep does -- unless multi=True and it passes
-    traj_batchable_multi: then it runs as ONE multi-source table engine (bfs_mode GS_BFS_MULTI)."""
+    traj_batchable_multi: then it runs as ONE multi-source table engine (bfs_mode GS_BFS_MULTI).
+    cluster: passed to every run_simulations call as its `cluster` (True, or "tables" for the view
+    per value of a batched share); the runner sees the results with their cluster_* arrays, the
+    reduced result keeps NAMES (allreduce_results does not carry the view)."""
     tdist, rank, world = _dist_info(group)
     runner = runner or run_simulations
     local = {}
@@ -330,6 +334,8 @@ def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_de
                 kw[k] = [x for c in cfgs for x in c[k]]
         if device is not None:
             kw["device"] = device
+        if cluster:
+            kw["cluster"] = cluster
         res = runner(stakes, n_sims=len(mine), fanouts=[int(c.get("fanout", 6)) for c in cfgs],
                      aszs=[int(c.get("asz", 12)) for c in cfgs], rot_probs=[float(c.get("p", 0.013333)) for c in cfgs],
                      **kw)
@@ -339,6 +345,8 @@ def run_traj_sweep(stakes, values, make_cfg, *, group=None, device=None, comm_de
         for i, kw in zip(mine, cfgs):
             if device is not None:
                 kw["device"] = device
+            if cluster:
+                kw["cluster"] = cluster
             res = runner(stakes, n_sims=1, **kw)
             local[i] = {(kind, name): (res.f64(0, name) if kind == "f" else res.u64(0, name)) for kind, name in NAMES}
     return allreduce_results(local, len(values), group=group, device=comm_device)
@@ -368,7 +376,7 @@ def trial_batchable_multi(cfgs, n_nodes):
 
 
 def run_trial_sweep(stakes, values, seeds, make_cfg, *, group=None, device=None, comm_device=None, runner=None,
-                    multi=False):
+                    multi=False, cluster=None):
     """A sweep repeated at several seeds (the reference's users repeat a configuration and look
     at the spread; here a repeat is a seed). Units are (value, seed) pairs, value-major: result
     index i_value * len(seeds) + i_seed. make_cfg(value) -> kwargs of run_simulations for that
@@ -376,7 +384,7 @@ def run_trial_sweep(stakes, values, seeds, make_cfg, *, group=None, device=None,
     make_cfg(None). Units are dealt round-robin over the ranks (shard) and each rank's share runs
     as ONE engine with a table per (size, probability, seed) when trial_batchable -- or, with
     multi=True, trial_batchable_multi (bfs_mode GS_BFS_MULTI) -- else one engine per unit.
-    Results are bit-identical either way."""
+    Results are bit-identical either way. cluster: as in run_traj_sweep."""
     tdist, rank, world = _dist_info(group)
     runner = runner or run_simulations
     seeds = [int(s) for s in seeds]
@@ -399,6 +407,8 @@ def run_trial_sweep(stakes, values, seeds, make_cfg, *, group=None, device=None,
                 kw[k] = [x for c in cfgs for x in c[k]]
         if device is not None:
             kw["device"] = device
+        if cluster:
+            kw["cluster"] = cluster
         res = runner(stakes, n_sims=len(mine), fanouts=[int(c.get("fanout", 6)) for c in cfgs],
                      aszs=[int(c.get("asz", 12)) for c in cfgs], rot_probs=[float(c.get("p", 0.013333)) for c in cfgs],
                      seeds=[c["seed"] for c in cfgs], **kw)
@@ -408,6 +418,8 @@ def run_trial_sweep(stakes, values, seeds, make_cfg, *, group=None, device=None,
         for i, kw in zip(mine, cfgs):
             if device is not None:
                 kw["device"] = device
+            if cluster:
+                kw["cluster"] = cluster
             res = runner(stakes, n_sims=1, **kw)
             local[i] = {(kind, name): (res.f64(0, name) if kind == "f" else res.u64(0, name)) for kind, name in NAMES}
     return allreduce_results(local, n_units, group=group, device=comm_device)

@@ -293,8 +293,8 @@ int gs_read_failed(gs_engine* e, uint32_t slot, uint8_t* failed /*[n]*/);
  * and I_r[v] with their nodes (the smallest id among equals) and the nodes with E_r[v] > 0.
  * All integer sums and maxima: exact, whatever the order of the reduction.
  * The view sums EVERY slot of the engine, whatever its table, fanout or threshold: it means
- * "load" only when the slots are origins of one configuration. Slot groups and weights per
- * origin are not provided.
+ * "load" only when the slots are origins of one configuration; gs_cluster_enable_groups
+ * (below) sums per group of slots, with a weight per slot.
  * gs_cluster_enable(on != 0) allocates the view (about 68 B per node and 56 B per recorded
  * round held on the device, counted in gs_engine_info's bytes and gs_engine_memory's
  * other_bytes) and zeroes it; it is allowed whenever gs_set_slots is, before or after it;
@@ -318,6 +318,40 @@ int gs_read_cluster_load(gs_engine* e, uint64_t* egress, uint64_t* ingress, uint
                          uint32_t* egress_peak, uint32_t* ingress_peak);
 /* *count = recorded rounds so far; GS_ERANGE when cap is smaller */
 int gs_read_cluster_rounds(gs_engine* e, gs_cluster_round* out, size_t cap, size_t* count);
+/* --- the view per slot group, with a weight per slot ---------------------------
+ * The slots are cut into n_groups groups of consecutive slots (group g: group_slots[g] slots
+ * behind those of the groups before it, as the trajectory tables are laid out) and slot j
+ * counts weights[j] times (u32; 0 excludes the slot; NULL = 1 each). Per group g:
+ *   E_r^g[v] = sum_{j in g} w_j eg_j[v], and I, P likewise;
+ *   D_r^g[v] = sum_{j in g} w_j [1 <= h_j[v] <= 254];  H_r^g[v] = sum of w_j h_j[v] over those j.
+ * Every group keeps what the ungrouped view keeps: totals, peaks and one gs_cluster_round per
+ * recorded round. group_slots == NULL with n_groups == 0: one group per trajectory table
+ * (gs_create_traj[_seeds]; one group on an engine made another way).
+ * gs_cluster_enable_groups is allowed whenever gs_cluster_enable is; allocation is all or nothing
+ * (GS_ENOMEM): about 68 B per node and 56 B per held round, each times n_groups, plus 12 B per
+ * slot chunk and 4 B per slot, counted like the ungrouped view's. GS_EINVAL (the message names
+ * the argument): counts that do not sum to n_slots, an empty group, n_groups > n_slots, a null
+ * group_slots with n_groups != 0. GS_ERANGE (the message names the group): a group whose
+ * (sum of weights) x max(255, inbound capacity) >= 2^32 -- the per-round sums stay u32 -- or
+ * more than 65,535 groups or slot chunks. GS_ESTATE: a partition rank; a view with another
+ * grouping or other weights is enabled (disable it first: gs_cluster_enable(e, 0) frees either
+ * kind); enabling the identical grouping again is a no-op. A view of one group and unit weights
+ * and gs_cluster_enable's are the same grouping: either call is a no-op after the other, and
+ * gs_cluster_enable(e, 1) over any other grouped view is GS_ESTATE. A refused call leaves the
+ * engine as it was. gs_set_slots zeroes every group; rounds recorded before enabling read as
+ * zero entries in every group. The round's reduction stays two launches, whatever n_groups.
+ * gs_cluster_groups reads the grouping back (*n_groups is set also when cap is too small:
+ * GS_ERANGE; weights [n_slots] or NULL); for gs_cluster_enable's view: 1 group, unit weights.
+ * The _group reads take the un-suffixed reads' arguments after g (g >= n_groups: GS_EINVAL);
+ * the un-suffixed reads return group 0 of a one-group view and GS_EINVAL when there are more. */
+int gs_cluster_enable_groups(gs_engine* e, const uint32_t* group_slots, uint32_t n_groups,
+                             const uint32_t* weights /*[n_slots] or NULL = 1*/);
+int gs_cluster_groups(gs_engine* e, uint32_t* group_slots, uint32_t cap, uint32_t* n_groups,
+                      uint32_t* weights /*[n_slots] or NULL*/);
+int gs_read_cluster_load_group(gs_engine* e, uint32_t g, uint64_t* egress, uint64_t* ingress, uint64_t* prunes,
+                               uint64_t* delivered, uint64_t* hop_sum, uint32_t* egress_peak,
+                               uint32_t* ingress_peak);
+int gs_read_cluster_rounds_group(gs_engine* e, uint32_t g, gs_cluster_round* out, size_t cap, size_t* count);
 /* Cluster::mst (gossip.rs:580-591): parent[v] = the node that first discovered v in the
  * reference's FIFO queue order, UINT32_MAX for the origin and unreached nodes (debug
  * readback after gs_run_gossip, n <= 262,144). */
@@ -499,6 +533,16 @@ int gs_run_simulations_cluster(const gs_sim_config* cfg, const uint64_t* stakes,
                                const double* fractions, const uint32_t* fanouts, const uint32_t* active_set_sizes,
                                const double* rotation_probabilities, const uint64_t* seeds /*per sim or NULL*/,
                                int cluster, gs_sim_result** out);
+/* The same with the view grouped by trajectory table (gs_cluster_enable_groups with one group per
+ * table; the sims of one (size, probability, seed) are one table, so one group) and a weight per
+ * sim (NULL = 1), permuted into table order with the sims. The cluster_* names under a sim answer
+ * with the arrays of that sim's own group. */
+int gs_run_simulations_cluster_tables(const gs_sim_config* cfg, const uint64_t* stakes, uint32_t n_nodes,
+                                      uint32_t n_sims, const uint32_t* origin_ranks, const uint32_t* min_ingress,
+                                      const double* thresholds, const double* fractions, const uint32_t* fanouts,
+                                      const uint32_t* active_set_sizes, const double* rotation_probabilities,
+                                      const uint64_t* seeds /*per sim or NULL*/,
+                                      const uint32_t* weights /*per sim or NULL*/, gs_sim_result** out);
 void gs_result_free(gs_sim_result* r);
 /* Named arrays of a finished sim (same names as the oracle): e.g. "coverage",
  * "rmr", "coverage_stats", "stranded", "hops_hist" ... Returns the element
