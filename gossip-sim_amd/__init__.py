@@ -97,6 +97,9 @@ EXPORTS = {
     "gs_kernel_hash": (C.c_char_p, []),
     "gs_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "gs_read_mst": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_tree_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_read_tree": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_read_tree_load": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "gs_create_part": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                  C.POINTER(C.c_void_p)]),
     "gs_part_sizes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -578,6 +581,38 @@ class Engine:
         for v in np.nonzero(parent != 0xFFFFFFFF)[0]:
             out.setdefault(int(parent[v]), []).append(int(v))
         return out
+
+    # --- delivery tree on the device (one-kernel round) ------------------------
+    def enable_tree(self, on=True):
+        """Allocates (or, on=False, frees) the delivery tree: from now on every recorded round()
+        also walks each slot's first-delivery tree on the device, ahead of the round kernel."""
+        _check(lib().gs_tree_enable(self.h, 1 if on else 0))
+
+    def tree(self, slot):
+        """parent[n] (u32) of the last recorded round: the node that first discovered each node
+        in the reference's queue order; 0xFFFFFFFF for the origin and unreached nodes."""
+        parent = np.zeros(self.n, dtype=np.uint32)
+        _check(lib().gs_read_tree(self.h, slot, _ptr(parent)))
+        return parent
+
+    def tree_children(self, slot):
+        """The tree in mst()'s format: {discoverer: sorted nodes it first discovered}."""
+        parent = self.tree(slot)
+        out = {}
+        for v in np.nonzero(parent != 0xFFFFFFFF)[0]:
+            out.setdefault(int(parent[v]), []).append(int(v))
+        return out
+
+    def tree_load(self, slot=None):
+        """(children, subtree, rounds): per node, the first deliveries it made and the nodes below
+        it in the tree (u64 [n]), summed over the `rounds` recorded rounds since set_slots; of one
+        slot, or (None) of every slot summed on the device."""
+        ch = np.zeros(self.n, dtype=np.uint64)
+        sub = np.zeros(self.n, dtype=np.uint64)
+        rounds = C.c_uint64()
+        _check(lib().gs_read_tree_load(self.h, 0xFFFFFFFF if slot is None else slot, _ptr(ch), _ptr(sub),
+                                       C.byref(rounds)))
+        return ch, sub, rounds.value
 
     def pushes(self, slot):
         """Cluster::pushes (gossip.rs:566-573): {src: sorted peers it pushed to}."""

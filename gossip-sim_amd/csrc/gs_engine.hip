@@ -83,6 +83,7 @@ static int dalloc(Engine& e, T** p, size_t count, int fill = 0) {
 static int flush_rot_clear(Engine* e);
 static int ensure_rot_ahead(Engine* e);
 static int cluster_zero(Engine* e);
+static int tree_zero(Engine* e);
 
 template <class T>
 static void dfree(Engine& e, T*& p, size_t count) {
@@ -847,6 +848,7 @@ static int reset_pair_state(Engine* e) {
   e->sum_used = 0;
   e->h_sum.clear();
   e->h_cl.clear();
+  if (int s = tree_zero(e)) return s;
   return cluster_zero(e);
 }
 
@@ -1181,6 +1183,113 @@ static int cluster_record(Engine* e) {
   return GS_OK;
 }
 
+// The delivery tree of the recorded one-kernel round about to be launched (gs_tree_wg.hip): on the
+// engine's stream ahead of the round kernel, so it walks the rows and masks the round's BFS will.
+static int tree_record(Engine* e) {
+  if (!e->tr_on) return GS_OK;
+  if ((e->tr_rounds + 1) * (uint64_t)e->N >= (1ull << 32))
+    return fail(GS_ERANGE, "delivery tree: (recorded rounds + 1) x n_nodes must stay below 2^32 (the per-pair "
+                           "subtree sums are u32); read the load and call gs_set_slots, or disable the tree");
+  hipEvent_t t0;
+  e->tbegin("tree", &t0);
+  hipError_t r = launch_tree_wg(*e, e->rot_clear_pending);
+  e->tend("tree", t0);
+  HIPC(r);
+  return GS_OK;  // (gs_round counts the round once the round kernel's launch succeeded too)
+}
+
+static int tree_zero(Engine* e) {
+  e->tr_rounds = 0;
+  if (!e->tr_on) return GS_OK;
+  HIPC(hipMemsetAsync(e->tr_parent, 0xFF, e->PAIRS * 4, e->st));
+  HIPC(hipMemsetAsync(e->tr_kids, 0, e->PAIRS * 4, e->st));
+  HIPC(hipMemsetAsync(e->tr_sub, 0, e->PAIRS * 4, e->st));
+  return GS_OK;
+}
+
+static void tree_free(Engine* e) {
+  const size_t b0 = e->dev_bytes;
+  dfree(*e, e->tr_parent, e->PAIRS);
+  dfree(*e, e->tr_kids, e->PAIRS);
+  dfree(*e, e->tr_sub, e->PAIRS);
+  e->pair_bytes -= b0 - e->dev_bytes;
+  e->tr_on = false;
+  e->tr_rounds = 0;
+}
+
+int gs_tree_enable(gs_engine* eh, int on) {
+  ENGINE(eh);
+  if (!on) {
+    if (!e->tr_on) return GS_OK;
+    HIPC(hipStreamSynchronize(e->st));
+    tree_free(e);
+    return GS_OK;
+  }
+  if (e->part_on) return fail(GS_ESTATE, "gs_tree_enable: a node-range partition rank runs no one-kernel round");
+  if (!e->fused)
+    return fail(GS_ESTATE, "gs_tree_enable: the delivery tree rides on the one-kernel round (gs_engine_round_kind == 1: "
+                           "GS_BFS_WORKGROUP within its LDS bound); gs_run_gossip + gs_read_mst serve the step-wise path");
+  if (e->tr_on) return GS_OK;
+  const uint32_t nmax = tree_wg_max_nodes(e->ASZP);
+  if (e->N > nmax || tree_wg_lds_bytes(e->N, e->ASZP) > TREE_LDS_MAX)
+    return fail(GS_ERANGE, "gs_tree_enable: the tree kernel keeps " + std::to_string(tree_wg_node_bytes(e->ASZP)) +
+                               " B of LDS per node: at this active-set size it serves at most " + std::to_string(nmax) +
+                               " nodes (160 KB)");
+  const size_t b0 = e->dev_bytes;
+  int s = dalloc(*e, &e->tr_parent, e->PAIRS, 0xFF);
+  if (!s) s = dalloc(*e, &e->tr_kids, e->PAIRS, 0);
+  if (!s) s = dalloc(*e, &e->tr_sub, e->PAIRS, 0);
+  e->pair_bytes += e->dev_bytes - b0;
+  if (s) {  // all three or none
+    const std::string msg = g_err;
+    HIPC(hipStreamSynchronize(e->st));
+    tree_free(e);
+    return fail(s, msg);
+  }
+  e->tr_on = true;
+  e->tr_rounds = 0;
+  HIPC(hipStreamSynchronize(e->st));
+  return GS_OK;
+}
+
+int gs_read_tree(gs_engine* eh, uint32_t slot, uint32_t* parent) {
+  ENGINE(eh);
+  if (slot >= e->S) return fail(GS_EINVAL, "slot out of range");
+  if (!parent) return fail(GS_EINVAL, "null argument");
+  if (!e->tr_on) return fail(GS_ESTATE, "the delivery tree is not enabled (gs_tree_enable)");
+  if (!e->tr_rounds) return fail(GS_ESTATE, "gs_read_tree: no round has been recorded since the tree was enabled or zeroed");
+  HIPC(hipMemcpyAsync(parent, e->tr_parent + (size_t)slot * e->N, (size_t)e->N * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  return check_err(e);
+}
+
+int gs_read_tree_load(gs_engine* eh, uint32_t slot, uint64_t* children, uint64_t* subtree, uint64_t* rounds) {
+  ENGINE(eh);
+  if (slot != UINT32_MAX && slot >= e->S) return fail(GS_EINVAL, "slot out of range");
+  if (!e->tr_on) return fail(GS_ESTATE, "the delivery tree is not enabled (gs_tree_enable)");
+  const size_t N = e->N;
+  if (rounds) *rounds = e->tr_rounds;
+  if (slot == UINT32_MAX) {  // every slot: summed on the device
+    DevScratch sc;
+    unsigned long long* d = nullptr;
+    if (!sc.get(&d, 2 * N * 8)) return fail(GS_ENOMEM, "gs_read_tree_load: scratch alloc");
+    HIPC(launch_tree_sum(*e, d, d + N));
+    if (children) HIPC(hipMemcpyAsync(children, d, N * 8, hipMemcpyDeviceToHost, e->st));
+    if (subtree) HIPC(hipMemcpyAsync(subtree, d + N, N * 8, hipMemcpyDeviceToHost, e->st));
+    HIPC(hipStreamSynchronize(e->st));  // (the scratch is freed on return)
+    return check_err(e);
+  }
+  std::vector<uint32_t> a(N), b(N);
+  HIPC(hipMemcpyAsync(a.data(), e->tr_kids + slot * N, N * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipMemcpyAsync(b.data(), e->tr_sub + slot * N, N * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  for (size_t v = 0; v < N; ++v) {
+    if (children) children[v] = a[v];
+    if (subtree) subtree[v] = b[v];
+  }
+  return check_err(e);
+}
+
 static int do_stats(Engine* e, int mode) {
   hipEvent_t t0;
   e->tbegin("stats", &t0);
@@ -1252,6 +1361,7 @@ static int round_ahead(Engine* e, uint32_t round, bool rec) {
   hipError_t r = launch_round_wg(*e, rec, e->sum_used, clr, &ra);
   e->tend("round", t0);
   HIPC(r);
+  if (rec && e->tr_on) ++e->tr_rounds;  // (gs_round launched this round's tree ahead of the kernel)
   std::swap(e->peers, e->peers2);
   std::swap(e->hl, e->hl2);
   e->rows2_pending = (int)par;
@@ -1347,7 +1457,7 @@ static int round_split(Engine* e, uint32_t round, bool rec) {
 
 int gs_round(gs_engine* eh, uint32_t round, int record) {
   ENGINE_NOJOIN(eh);
-  if (e->split_ok && e->fused && !e->cl_on && !e->part_on && round < (1u << 27) && e->slots_set)
+  if (e->split_ok && e->fused && !e->cl_on && !e->tr_on && !e->part_on && round < (1u << 27) && e->slots_set)
     return round_split(e, round, record != 0);
   if (int s = split_join(e)) return s;
   if (int s = refuse_part(e)) return s;
@@ -1362,6 +1472,8 @@ int gs_round(gs_engine* eh, uint32_t round, int record) {
       e->peers2 = e->rows3[o];
       e->hl2 = e->hl3[o];
     }
+    if (rec)  // the delivery tree of this round, ahead of the round kernel on either launch path below
+      if (int s = tree_record(e)) return s;
     if (e->rot_ahead_ok && !(e->rot_have_prev && (round & 1u) == e->rot_parity)) return round_ahead(e, round, rec);
     hipEvent_t t0;
     e->tbegin("round", &t0);
@@ -1369,6 +1481,7 @@ int gs_round(gs_engine* eh, uint32_t round, int record) {
     hipError_t r = launch_round_wg(*e, rec, e->sum_used, clr);
     e->tend("round", t0);
     HIPC(r);
+    if (rec && e->tr_on) ++e->tr_rounds;  // (tree_record launched this round's tree above)
     e->rot_clear_pending = false;
     e->inb_valid = false;
     e->tbegin("rotate", &t0);
@@ -1992,7 +2105,7 @@ int gs_engine_round_kind(gs_engine* eh, uint32_t* fused) {
 int gs_engine_round_split(gs_engine* eh, uint32_t* out, size_t n) {
   ENGINE(eh);
   if (!out || n < 3) return fail(GS_EINVAL, "gs_engine_round_split: need 3 words");
-  const bool on = e->split_ok && e->fused && !e->cl_on && !e->part_on;  // (what gs_round checks)
+  const bool on = e->split_ok && e->fused && !e->cl_on && !e->tr_on && !e->part_on;  // (what gs_round checks)
   out[0] = on ? 1u : 0u;
   out[1] = on ? e->split_s0 : 0u;
   out[2] = on ? e->S - e->split_s0 : 0u;

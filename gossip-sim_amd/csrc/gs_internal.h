@@ -294,6 +294,14 @@ struct Engine {
   ClusterChunk* cl_chunks = nullptr;   // [cl_nchunks] gs_cluster_plan.h
   uint32_t cl_nchunks = 0;
   uint32_t* cl_wts = nullptr;          // [S]
+  // delivery tree (gs_tree_enable, gs_tree_wg.hip): first-discoverer parents and relay load per pair
+  bool tr_on = false;
+  uint32_t* tr_parent = nullptr;       // [PAIRS] the last recorded round's parents (UINT32_MAX: origin / unreached)
+  uint32_t* tr_kids = nullptr;         // [PAIRS] first deliveries made, summed over the recorded rounds
+  uint32_t* tr_sub = nullptr;          // [PAIRS] nodes below in the tree, summed over the recorded rounds
+  uint64_t tr_rounds = 0;              // recorded rounds since gs_set_slots (or the enable)
+  size_t tr_attr_lds = 0;              // dynamic LDS the tree kernel was last configured for ...
+  int tr_attr_fp = 0;                  // ... and for which push-column count (instantiation)
   uint32_t* err = nullptr;
   uint32_t* h_err = nullptr;  // pinned
   unsigned long long* phase_clk = nullptr;  // GS_PHASE_PROFILE=1: per-phase workgroup clock sums
@@ -442,6 +450,14 @@ hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_index, bool rot_
                            const SplitLaunch* sl = nullptr);
 size_t round_wg_lds_bytes(uint32_t N, uint32_t fcap, uint32_t ASZP);
 size_t bfs_wg_lds_bytes(uint32_t N);
+// delivery tree (gs_tree_wg.hip): the ordered BFS of the recorded round about to run (the round's
+// own arguments: the same rows, masks and pending rotation clear), and the sum over slots
+constexpr size_t TREE_LDS_MAX = 160 * 1024;
+size_t tree_wg_lds_bytes(uint32_t N, uint32_t ASZP);
+uint32_t tree_wg_node_bytes(uint32_t ASZP);
+uint32_t tree_wg_max_nodes(uint32_t ASZP);
+hipError_t launch_tree_wg(Engine& e, bool rot_clear);
+hipError_t launch_tree_sum(Engine& e, unsigned long long* kids, unsigned long long* sub);
 // cluster load view (gs_cluster.hip): the recorded round's reduction over slots and its fold
 hipError_t launch_cluster_view(Engine& e, uint32_t rec_index);
 uint32_t cluster_chunk_slots(uint32_t NP, uint32_t S);

@@ -26,6 +26,7 @@
 
 #include "gs_device.h"
 #include "gs_internal.h"
+#include "gs_round_args.h"
 
 namespace gs {
 
@@ -34,9 +35,6 @@ namespace gs {
 #endif
 #ifndef RWG_MIN_WAVES
 #define RWG_MIN_WAVES (RWG_THREADS_N / 128)  // waves per SIMD at 2 workgroups per CU (the LDS limit at C2)
-#endif
-#ifndef GS_NT_STORES
-#define GS_NT_STORES 1
 #endif
 constexpr uint32_t RWG_THREADS = RWG_THREADS_N;
 constexpr uint32_t RWG_WAVES = RWG_THREADS / 64;
@@ -54,80 +52,7 @@ constexpr uint32_t LANE_C = 16;    // register path: in-degree <= 16
 constexpr int LANE_L = 16;         // register prune path: cache entry <= 16 keys (the wave path
                                    // takes longer entries; at prune time they are rare)
 
-struct RoundArgs {
-  const uint64_t* stake;
-  const uint8_t* bucket;
-  const uint32_t* peers;
-  const uint16_t* hl;
-  const uint32_t* frank;
-  const uint32_t* srank;
-  const uint32_t* by_srank;
-  const uint32_t* prank;     // rank by (stake desc, id asc): the prune order's tie-broken stake key
-  const uint32_t* by_prank;
-  const uint64_t* pstake;    // stake by prune rank
-  const uint4* rinfo;        // by prune rank: {node id, 0, stake lo, stake hi}
-  const uint32_t* origin;
-  const uint8_t* obkt;
-  const uint32_t* nfail;
-  const uint32_t* min_ingress;
-  const double* thr;
-  uint32_t* slot_prunes;
-  uint8_t* hops;
-  uint32_t* cnt;
-  uint32_t* mask;
-  uint32_t* cmeta;
-  uint32_t* ckey;  // [CACHE_CAP][PAIRS] slot words (ck_make)
-  uint8_t* egress;
-  uint8_t* prune_round;
-  uint32_t* egress_acc;
-  uint32_t* ingress_acc;
-  uint32_t* prune_acc;
-  uint32_t* strand;
-  uint64_t* hist_acc;
-  gs_round_summary* sum;  // this round's row [S] of the summary ring (record only)
-  // the last rotation's pending prune-bit clear (null when none): replaced ring slots
-  // of rotated node u's entry k are rot_changed[u * 25 + k]
-  const uint32_t* rot_list;
-  const uint32_t* rot_count;
-  const uint32_t* rot_changed;
-  // rotation ahead (rot_on): workgroup 0 runs Cluster::chance_to_rotate of round rround on
-  // the other row buffer (rpeers / rhl), after copying the previous ahead rotation's
-  // entries (plist / pcount) into it from the current one
-  uint32_t rot_on;
-  const uint64_t* P;
-  const uint32_t* IX;
-  uint32_t* rpeers;
-  uint16_t* rhl;
-  uint32_t* rlist;
-  uint32_t* rcount;
-  uint32_t* rchanged;
-  const uint32_t* plist;
-  const uint32_t* pcount;
-  uint64_t seed;
-  double rp;
-  uint32_t rround;
-  uint32_t* err;
-  unsigned long long* phase_clk;  // optional: per-phase clock sums (thread 0 of each workgroup)
-  uint32_t wave_c_max;            // in-degree bound of the wave consume path (64; 24 for path coverage)
-  uint32_t N, S, ASZ, fanout, fcap;
-  size_t PAIRS;
-  int record;
-  const uint32_t* sfan;  // [S] per-slot fanouts while they differ (the PF kernels), else null: every slot takes `fanout`
-  // several trajectory tables (the MT kernels; else null): slot o reads table stab[o] -- peers / hl /
-  // rpeers / rhl hold the tables t_rows words / t_ents entries apart, the rotation lists N words,
-  // the changed bits t_ents words and the counters 2 words apart -- with ttab[t]'s size and
-  // probability; rot_on is then the number of tables (one leading rotation workgroup each).
-  // ttab[t].seed is the table's Philox key (the MT kernels draw DECIDE and ROTATE on it) and frank
-  // holds the tables' fail ranks t_frank words apart (0: one array, the tables' keys are equal)
-  const uint32_t* stab;
-  const TrajDev* ttab;
-  size_t t_rows, t_ents, t_frank;
-  // round split (last, so that every other argument keeps its place): the ahead rotation before
-  // plist's, whose entries the rotation workgroup copies too -- with three row generations the
-  // other buffer is two rotations behind the current one (null: one rotation, or none)
-  const uint32_t* plist2;
-  const uint32_t* pcount2;
-};
+// (RoundArgs, the kernel's argument block, and ntl / nts: gs_round_args.h)
 
 // Phase clock: thread 0 adds the time since the last mark to phase_clk[ph].
 #define RWG_MARK(ph)                                                              \
@@ -170,20 +95,6 @@ __host__ __device__ inline bool rwg_off16(uint32_t N, uint32_t fcap) { return (u
 
 size_t round_wg_lds_bytes(uint32_t N, uint32_t fcap, uint32_t ASZP) {
   return rwg_layout(N, fcap, ASZP <= 16 ? 2 : 4, rwg_off16(N, fcap) ? 2 : 4).total;
-}
-
-// Streaming per-pair state (read or written once per round, ~0.5 GB/round at C2)
-// goes through non-temporal loads/stores so that it does not evict the shared
-// active-set rows (3.6 MB at C2) from L2.
-template <class T>
-__device__ inline T ntl(const T* p) { return __builtin_nontemporal_load(p); }
-template <class T>
-__device__ inline void nts(T* p, T v) {
-#if GS_NT_STORES
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 
 // ctrl words
@@ -1230,8 +1141,8 @@ static hipError_t launch_rwg(Engine& e, const RoundArgs& a, size_t lds, const Rw
   return launch_rwg_fp<ASZP, OFF16, ASZP>(e, a, lds, g);
 }
 
-hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_clear, const RotAhead* ra,
-                           const SplitLaunch* sl) {
+RoundArgs round_args(Engine& e, bool record, uint32_t rec_slot, bool rot_clear, const RotAhead* ra,
+                     const SplitLaunch* sl) {
   RoundArgs a;
   a.rot_on = ra && (!sl || sl->rot) ? e.T : 0u;  // (one leading rotation workgroup per trajectory table)
   a.stab = e.T > 1 ? e.stab : nullptr; a.ttab = e.ttab; a.t_rows = e.t_rows; a.t_ents = e.t_ents;
@@ -1255,7 +1166,6 @@ hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_c
   a.err = e.err; a.phase_clk = e.phase_clk;
   a.wave_c_max = (e.prm.flags & GS_FLAG_NARROW_WAVE_PATH) ? 24u : 64u; a.N = e.N; a.S = e.S; a.ASZ = e.ASZ; a.fanout = e.fanout; a.sfan = e.fvar ? e.sfan : nullptr; a.fcap = e.fcap; a.PAIRS = e.PAIRS;
   a.record = record ? 1 : 0;
-  RwgGrid g{e.S + a.rot_on, e.st};
   if (sl) {  // one slot group: the kernel's slot index starts at 0, so everything it indexes by slot
              // or by (slot, node) pair starts at the group's first slot (ckey keeps its PAIRS stride)
     const size_t s0 = sl->s0, p0 = s0 * e.N;
@@ -1266,9 +1176,14 @@ hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_c
     a.hops += p0; a.cnt += p0; a.mask += p0; a.cmeta += p0; a.ckey += p0; a.egress += p0; a.prune_round += p0;
     a.egress_acc += p0; a.ingress_acc += p0; a.prune_acc += p0; a.strand += p0;
     a.S = sl->ns;
-    g.blocks = sl->ns + a.rot_on;
-    g.st = sl->st;
   }
+  return a;
+}
+
+hipError_t launch_round_wg(Engine& e, bool record, uint32_t rec_slot, bool rot_clear, const RotAhead* ra,
+                           const SplitLaunch* sl) {
+  const RoundArgs a = round_args(e, record, rec_slot, rot_clear, ra, sl);
+  const RwgGrid g{a.S + a.rot_on, sl ? sl->st : e.st};
   const size_t lds = round_wg_lds_bytes(e.N, e.fcap, e.ASZP);
   hipError_t r;
   const bool off16 = rwg_off16(e.N, e.fcap);

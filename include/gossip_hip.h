@@ -356,8 +356,40 @@ int gs_read_cluster_rounds_group(gs_engine* e, uint32_t g, gs_cluster_round* out
  * reference's FIFO queue order, UINT32_MAX for the origin and unreached nodes (debug
  * readback after gs_run_gossip, n <= 262,144). */
 int gs_read_mst(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
+/* --- delivery tree on the device: first-discoverer parents and relay load -----
+ * The same tree (Cluster::mst) for the one-kernel round, every slot at once: while enabled,
+ * every RECORDED gs_round launches one more kernel (family "tree") on the engine's stream ahead
+ * of the round kernel, one workgroup per slot, which walks the rows, prune masks (with the last
+ * rotation's pending clear), failed ranks and per-slot fanouts the round's BFS will see, in the
+ * reference's FIFO queue order, and keeps per (slot, node) pair
+ *   parent        of the last recorded round (UINT32_MAX: the origin and unreached nodes),
+ *   children[v]   first deliveries v made (its outbound degree in the tree),
+ *   subtree[v]    nodes below v in the tree (the relay load: deliveries that depend on v),
+ * the last two summed over the recorded rounds since gs_set_slots (which zeroes them and the
+ * round count). gs_tree_enable(on != 0) allocates the three arrays (12 B per pair, counted in
+ * gs_engine_info's bytes and gs_engine_memory's pair_bytes) and zeroes them; enabling an enabled
+ * tree is a no-op; on == 0 frees them. Rounds that are not recorded launch nothing, an engine
+ * that never enables the tree allocates and launches nothing, and the round split is off while
+ * the tree is on (gs_engine_round_split reports it). GS_ESTATE: gs_round is not the one-kernel
+ * round (gs_engine_round_kind == 0), or a partition rank. GS_ERANGE: more nodes than the
+ * kernel's LDS holds (14 B per node, 16 B with more than 16 ring slots, of 160 KB; the message
+ * names the bound), and a recorded round once (recorded rounds + 1) x n_nodes >= 2^32 (the
+ * per-pair sums are u32). The round count rises once the round kernel's launch has succeeded;
+ * after a gs_round that returned an error the tree's arrays are unspecified, like the engine's
+ * other results. A slot that passes the 253-hop limit writes no tree that round (its parents stay
+ * the previous round's, its sums lack the round) and the round's error is reported as before, by
+ * the next gs_sync or readback (GS_ERANGE), these reads included.
+ * gs_read_tree returns the last recorded round's parents (GS_ESTATE: not enabled, or no round
+ * recorded yet); gs_read_tree_load the totals of one slot, or with slot == UINT32_MAX of every
+ * slot summed on the device, and the number of recorded rounds (any pointer may be NULL).
+ * gs_read_mst and the step-wise path are unchanged. */
+int gs_tree_enable(gs_engine* e, int on);
+int gs_read_tree(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
+int gs_read_tree_load(gs_engine* e, uint32_t slot, uint64_t* children /*[n]*/, uint64_t* subtree /*[n]*/,
+                      uint64_t* rounds);
 /* GS_FLAG_PROFILE: summed device time of a kernel family ("bfs", "consume",
- * "rotate", "stats", "cluster": the cluster load view's two launches per recorded round)
+ * "rotate", "stats", "cluster": the cluster load view's two launches per recorded round,
+ * "tree": the delivery tree's launch per recorded round)
  * since the last reset, and its launch count. */
 int gs_kernel_time(gs_engine* e, const char* family, double* ms, uint64_t* launches);
 int gs_kernel_time_reset(gs_engine* e);
