@@ -98,6 +98,7 @@ EXPORTS = {
     "gs_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "gs_read_mst": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_tree_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_tree_enable_records": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_read_tree": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_read_tree_load": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "gs_create_part": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -583,10 +584,13 @@ class Engine:
         return out
 
     # --- delivery tree on the device (one-kernel round) ------------------------
-    def enable_tree(self, on=True):
+    def enable_tree(self, on=True, records=False):
         """Allocates (or, on=False, frees) the delivery tree: from now on every recorded round()
-        also walks each slot's first-delivery tree on the device, ahead of the round kernel."""
-        _check(lib().gs_tree_enable(self.h, 1 if on else 0))
+        also walks each slot's first-delivery tree on the device, ahead of the round kernel.
+        records=True: the mode of the engines whose round() launches the step kernels (any node
+        count): the tree is built from the BFS's inbound records, between BFS and consume."""
+        fn = lib().gs_tree_enable_records if records else lib().gs_tree_enable
+        _check(fn(self.h, 1 if on else 0))
 
     def tree(self, slot):
         """parent[n] (u32) of the last recorded round: the node that first discovered each node

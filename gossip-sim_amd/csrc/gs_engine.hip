@@ -130,6 +130,7 @@ static void destroy_engine(Engine* e) {
   if (e->x_pin) hipHostFree(e->x_pin);
   if (e->mv_hlvl) hipHostFree(e->mv_hlvl);
   if (e->mv_prof) hipHostFree(e->mv_prof);
+  if (e->trr_hmeta) hipHostFree(e->trr_hmeta);
   if (e->pb_registered) pb_register(*e, false);
   for (auto& kv : e->timers)
     for (auto& pr : kv.second.ev) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
@@ -1212,8 +1213,15 @@ static void tree_free(Engine* e) {
   dfree(*e, e->tr_parent, e->PAIRS);
   dfree(*e, e->tr_kids, e->PAIRS);
   dfree(*e, e->tr_sub, e->PAIRS);
+  for (uint32_t** p : {&e->trr_q, &e->trr_qpos, &e->trr_lst, &e->trr_cmask, &e->trr_pt, &e->trr_ex})
+    dfree(*e, *p, e->PAIRS);  // (records mode's per-pair scratch)
   e->pair_bytes -= b0 - e->dev_bytes;
-  e->tr_on = false;
+  dfree(*e, e->trr_btot, tree_rec_btot_words(*e));
+  dfree(*e, e->trr_lv, tree_rec_lv_words(*e));
+  dfree(*e, e->trr_meta, tree_rec_meta_words(*e));
+  if (e->trr_hmeta) hipHostFree(e->trr_hmeta);
+  e->trr_hmeta = nullptr;
+  e->tr_on = e->tr_rec = false;
   e->tr_rounds = 0;
 }
 
@@ -1228,7 +1236,8 @@ int gs_tree_enable(gs_engine* eh, int on) {
   if (e->part_on) return fail(GS_ESTATE, "gs_tree_enable: a node-range partition rank runs no one-kernel round");
   if (!e->fused)
     return fail(GS_ESTATE, "gs_tree_enable: the delivery tree rides on the one-kernel round (gs_engine_round_kind == 1: "
-                           "GS_BFS_WORKGROUP within its LDS bound); gs_run_gossip + gs_read_mst serve the step-wise path");
+                           "GS_BFS_WORKGROUP within its LDS bound); gs_tree_enable_records serves the step-wise round");
+  if (e->tr_rec) return fail(GS_ESTATE, "gs_tree_enable: the records mode (gs_tree_enable_records) is on");
   if (e->tr_on) return GS_OK;
   const uint32_t nmax = tree_wg_max_nodes(e->ASZP);
   if (e->N > nmax || tree_wg_lds_bytes(e->N, e->ASZP) > TREE_LDS_MAX)
@@ -1250,6 +1259,57 @@ int gs_tree_enable(gs_engine* eh, int on) {
   e->tr_rounds = 0;
   HIPC(hipStreamSynchronize(e->st));
   return GS_OK;
+}
+
+// The records mode (gs_tree_rec.hip): the same tree for the engines whose gs_round launches the step
+// kernels, from the BFS's inbound records.
+int gs_tree_enable_records(gs_engine* eh, int on) {
+  ENGINE(eh);
+  if (!on) return gs_tree_enable(eh, 0);
+  if (e->part_on) return fail(GS_ESTATE, "gs_tree_enable_records: a node-range partition rank keeps only its own nodes' records");
+  if (e->fused)
+    return fail(GS_ESTATE, "gs_tree_enable_records: the one-kernel round (gs_engine_round_kind == 1) keeps its inbound "
+                           "records on-chip; gs_tree_enable serves it");
+  if (e->bfs_mode == GS_BFS_MULTI && e->mv_fused)
+    return fail(GS_ESTATE, "gs_tree_enable_records: the fused gather + consume (GS_MV_FUSED=1) never writes the inbound "
+                           "rows to HBM");
+  if (e->tr_on && !e->tr_rec) return fail(GS_ESTATE, "gs_tree_enable_records: the one-kernel mode (gs_tree_enable) is on");
+  if (e->tr_on) return GS_OK;
+  const size_t b0 = e->dev_bytes;
+  int s = dalloc(*e, &e->tr_parent, e->PAIRS, 0xFF);
+  if (!s) s = dalloc(*e, &e->tr_kids, e->PAIRS, 0);
+  if (!s) s = dalloc(*e, &e->tr_sub, e->PAIRS, 0);
+  for (uint32_t** p : {&e->trr_q, &e->trr_qpos, &e->trr_lst, &e->trr_cmask, &e->trr_pt, &e->trr_ex})
+    if (!s) s = dalloc(*e, p, e->PAIRS, 0);  // (zero: every stale queue entry is a node id)
+  e->pair_bytes += e->dev_bytes - b0;
+  if (!s) s = dalloc(*e, &e->trr_btot, tree_rec_btot_words(*e), 0);
+  if (!s) s = dalloc(*e, &e->trr_lv, tree_rec_lv_words(*e), 0);
+  if (!s) s = dalloc(*e, &e->trr_meta, tree_rec_meta_words(*e), 0);
+  if (!s && hipHostMalloc(&e->trr_hmeta, 257 * 4) != hipSuccess) s = fail(GS_ENOMEM, "gs_tree_enable_records: pinned alloc");
+  if (s) {  // all or none
+    const std::string msg = g_err;
+    HIPC(hipStreamSynchronize(e->st));
+    tree_free(e);
+    return fail(s, msg);
+  }
+  e->tr_on = e->tr_rec = true;
+  e->tr_rounds = 0;
+  HIPC(hipStreamSynchronize(e->st));
+  return GS_OK;
+}
+
+// The records-mode pass of a recorded step-wise round: behind its BFS, ahead of its consume.
+static int tree_rec_record(Engine* e) {
+  if (!e->tr_rec) return GS_OK;
+  if ((e->tr_rounds + 1) * (uint64_t)e->N >= (1ull << 32))
+    return fail(GS_ERANGE, "delivery tree: (recorded rounds + 1) x n_nodes must stay below 2^32 (the per-pair "
+                           "subtree sums are u32); read the load and call gs_set_slots, or disable the tree");
+  hipEvent_t t0;
+  e->tbegin("tree", &t0);
+  hipError_t r = launch_tree_rec(*e, &e->trr_launches);
+  e->tend("tree", t0);
+  HIPC(r);
+  return GS_OK;  // (gs_round counts the round once its other launches succeeded too)
 }
 
 int gs_read_tree(gs_engine* eh, uint32_t slot, uint32_t* parent) {
@@ -1506,9 +1566,12 @@ int gs_round(gs_engine* eh, uint32_t round, int record) {
     HIPC(r);
   } else {
     if (int s = do_bfs(e, rec)) return s;
+    if (rec)  // the delivery tree from this BFS's records, under the masks it saw
+      if (int s = tree_rec_record(e)) return s;
     if (int s = do_cp(e, true, true, true, rec)) return s;
   }
   if (int s = gs_chance_to_rotate(eh, round)) return s;
+  if (rec && e->tr_rec) ++e->tr_rounds;
   if (rec) return do_stats(e, e->bfs_mode == GS_BFS_WORKGROUP ? 2 : mv_layout(*e) ? 4 : 1);
   return GS_OK;
 }
@@ -2050,6 +2113,11 @@ int gs_kernel_time(gs_engine* eh, const char* family, double* ms, uint64_t* laun
     HIPC(hipMemcpy(v, e->phase_clk, sizeof(v), hipMemcpyDeviceToHost));
     *ms = (double)v[ph] * 1e-5;
     *launches = e->timers["round"].n;
+    return GS_OK;
+  }
+  if (family && std::strcmp(family, "tree.kernels") == 0) {  // kernels of the last records-mode tree pass
+    *ms = 0;
+    *launches = e->trr_launches;
     return GS_OK;
   }
   if (family && std::strcmp(family, "round") == 0 && e->split_t_n) {

@@ -302,6 +302,14 @@ struct Engine {
   uint64_t tr_rounds = 0;              // recorded rounds since gs_set_slots (or the enable)
   size_t tr_attr_lds = 0;              // dynamic LDS the tree kernel was last configured for ...
   int tr_attr_fp = 0;                  // ... and for which push-column count (instantiation)
+  // records mode (gs_tree_enable_records, gs_tree_rec.hip): the same three arrays, filled from the
+  // step-wise round's inbound records; its scratch, 24 B per pair and the small per-slot tables
+  bool tr_rec = false;
+  uint32_t *trr_q = nullptr, *trr_qpos = nullptr, *trr_lst = nullptr;  // [PAIRS] FIFO queue, node positions, nodes by level
+  uint32_t *trr_cmask = nullptr, *trr_pt = nullptr, *trr_ex = nullptr; // [PAIRS] child bits, parent | take << 24, scan / subtree
+  uint32_t *trr_btot = nullptr, *trr_lv = nullptr, *trr_meta = nullptr;  // scan block totals, level starts, histogram
+  uint32_t* trr_hmeta = nullptr;       // pinned [257]: the deepest level and each level's widest slot
+  uint32_t trr_launches = 0;           // kernels of the last recorded round's pass
   uint32_t* err = nullptr;
   uint32_t* h_err = nullptr;  // pinned
   unsigned long long* phase_clk = nullptr;  // GS_PHASE_PROFILE=1: per-phase workgroup clock sums
@@ -458,6 +466,12 @@ uint32_t tree_wg_node_bytes(uint32_t ASZP);
 uint32_t tree_wg_max_nodes(uint32_t ASZP);
 hipError_t launch_tree_wg(Engine& e, bool rot_clear);
 hipError_t launch_tree_sum(Engine& e, unsigned long long* kids, unsigned long long* sub);
+// ... from the inbound records of the step-wise round's BFS (gs_tree_rec.hip): the whole pass of
+// one recorded round, and the sizes of its small tables
+hipError_t launch_tree_rec(Engine& e, uint32_t* launches);
+size_t tree_rec_meta_words(const Engine& e);
+size_t tree_rec_lv_words(const Engine& e);
+size_t tree_rec_btot_words(const Engine& e);
 // cluster load view (gs_cluster.hip): the recorded round's reduction over slots and its fold
 hipError_t launch_cluster_view(Engine& e, uint32_t rec_index);
 uint32_t cluster_chunk_slots(uint32_t NP, uint32_t S);

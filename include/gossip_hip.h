@@ -384,6 +384,25 @@ int gs_read_mst(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
  * slot summed on the device, and the number of recorded rounds (any pointer may be NULL).
  * gs_read_mst and the step-wise path are unchanged. */
 int gs_tree_enable(gs_engine* e, int on);
+/* The same tree where gs_round launches the step kernels (gs_engine_round_kind == 0: the level,
+ * binned, multi-source and hybrid BFS, and GS_BFS_WORKGROUP under GS_FLAG_SPLIT_ROUND), at any
+ * node count: while enabled, every RECORDED gs_round runs the tree pass (family "tree") on the
+ * engine's stream between its BFS and its consume, for every slot at once, from what the BFS
+ * left in HBM: hops, in-degrees and inbound records, with the rows and prune masks the BFS saw.
+ * Launches per round: 5 + 5 per BFS level, no sort and no wait between workgroups; the host
+ * reads 1 KB back once per recorded round (the deepest level and each level's widest slot).
+ * It fills gs_tree_enable's three arrays (12 B per pair) and keeps 24 B per pair of scratch (the
+ * FIFO queue, node positions, nodes by level, child bits, parent | take index, scan counts),
+ * 36 B per pair in all, counted in gs_engine_info's bytes and gs_engine_memory's pair_bytes;
+ * the per-slot tables beside them (level starts, histogram, scan block totals: about 3 KB per
+ * slot + n / 64 B) count as other bytes. gs_read_tree, gs_read_tree_load, gs_set_slots' zeroing,
+ * the 2^32 refusal, the round count and the 253-hop rule are gs_tree_enable's; on == 0 (of either
+ * call) frees everything. GS_ESTATE: a one-kernel-round engine, a partition rank, the multi-source
+ * BFS with the fused gather + consume (its inbound rows never reach HBM), or gs_tree_enable's mode
+ * is on. A recorded push that its pusher's row does not take raises the engine's bounds error
+ * (GS_ERANGE at the next read). gs_kernel_time("tree.kernels") gives the kernels the last pass
+ * launched (in `launches`). gs_run_gossip and gs_read_mst are unchanged. */
+int gs_tree_enable_records(gs_engine* e, int on);
 int gs_read_tree(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
 int gs_read_tree_load(gs_engine* e, uint32_t slot, uint64_t* children /*[n]*/, uint64_t* subtree /*[n]*/,
                       uint64_t* rounds);
