@@ -162,6 +162,10 @@ EXPORTS = {
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_read_cluster_rounds_group": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
                                                C.POINTER(C.c_size_t)]),
+    "gs_reach_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_reach_enable_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_read_reach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.POINTER(C.c_uint64)]),
     "gs_destroy": (None, [C.c_void_p]),
     "gs_set_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "gs_set_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -694,6 +698,36 @@ class Engine:
                 continue
             _check(rc)
             return out[:cnt.value]
+
+    # --- stake reach view (nodes and stake per hop, summed over a group's slots) ---
+    def enable_reach(self, on=True, groups=None, weights=None):
+        """Allocates (or, on=False, frees) the stake reach view: from now on every recorded round
+        also sums, per slot group and hop byte, the nodes at that hop and their stake on the
+        device. groups / weights: as enable_cluster_view's (the two views are independent)."""
+        if not on:
+            if groups is not None or weights is not None:
+                raise ValueError("enable_reach: groups / weights go with on=True")
+            _check(lib().gs_reach_enable(self.h, 0))
+            return
+        if groups is None and weights is None:
+            _check(lib().gs_reach_enable(self.h, 1))
+            return
+        g, w = cluster_group_args(self.n_slots, groups, weights)
+        _check(lib().gs_reach_enable_groups(self.h, None if g is None else _ptr(g), 0 if g is None else len(g),
+                                            None if w is None else _ptr(w)))
+
+    def reach(self, group=None):
+        """Slot group `group` (None: group 0) of the reach view, per hop byte 0..255 (0: the
+        origins, 255: unreached): nodes / stake over the recorded rounds since set_slots,
+        last_nodes / last_stake of the last recorded round, and rounds, their count. nodes are
+        u64 [256]; stake values pass 2^64, so they are object arrays of Python ints."""
+        a = {k: np.zeros(256, dtype=np.uint64) for k in ("nodes", "lo", "hi", "last_nodes", "last_lo", "last_hi")}
+        rounds = C.c_uint64()
+        _check(lib().gs_read_reach(self.h, 0 if group is None else _group_index(group), *[_ptr(v) for v in a.values()],
+                                   C.byref(rounds)))
+        wide = lambda lo, hi: np.array([int(h) << 64 | int(l) for l, h in zip(lo, hi)], dtype=object)
+        return {"nodes": a["nodes"], "stake": wide(a["lo"], a["hi"]), "last_nodes": a["last_nodes"],
+                "last_stake": wide(a["last_lo"], a["last_hi"]), "rounds": int(rounds.value)}
 
     def failed(self, slot):
         out = np.zeros(self.n, dtype=np.uint8)

@@ -33,6 +33,36 @@ def stake_weights(stakes, origins, scale=1000):
     return np.array(out, dtype=np.uint32)
 
 
+def reach_curve(reach, fractions=(1 / 3, 1 / 2, 2 / 3)):
+    """The stake-weighted latency curve of Engine.reach()'s "stake" and "nodes" ([256] per hop
+    byte; pass the last_* arrays under these keys for one round's curve). Returns a dict:
+      stake / nodes   f64 [255]: the share reached within h hops, h = 0..254, of the total that
+                      includes bin 255 (unreached); zeros when the total is 0
+      hops_to         {fraction: the smallest h whose cumulative stake is >= fraction x total, or
+                      None if no h <= 254 reaches it}, compared in integers (a float fraction is
+                      the exact rational it holds)."""
+    from fractions import Fraction
+    out = {}
+    cum = {}
+    for k in ("stake", "nodes"):
+        a = [int(x) for x in reach[k]]
+        if len(a) != 256:
+            raise ValueError(f"reach_curve: {k} needs 256 bins")
+        total, run, c = sum(a), 0, []
+        for x in a[:255]:
+            run += x
+            c.append(run)
+        cum[k] = (c, total)
+        out[k] = np.array([float(Fraction(x, total)) if total else 0.0 for x in c])
+    c, total = cum["stake"]
+    out["hops_to"] = {}
+    for f in fractions:
+        q = Fraction(f)
+        out["hops_to"][f] = next((h for h, x in enumerate(c) if total and x * q.denominator >= q.numerator * total),
+                                 None)
+    return out
+
+
 def _spread(a):
     """min / median / p99 / max of a per-node array; the p99 is the value of rank
     ceil(0.99 n) in ascending order (an element of the array, no interpolation)."""

@@ -84,6 +84,7 @@ static int flush_rot_clear(Engine* e);
 static int ensure_rot_ahead(Engine* e);
 static int cluster_zero(Engine* e);
 static int tree_zero(Engine* e);
+static int reach_zero(Engine* e);
 
 template <class T>
 static void dfree(Engine& e, T*& p, size_t count) {
@@ -850,6 +851,7 @@ static int reset_pair_state(Engine* e) {
   e->h_sum.clear();
   e->h_cl.clear();
   if (int s = tree_zero(e)) return s;
+  if (int s = reach_zero(e)) return s;
   return cluster_zero(e);
 }
 
@@ -1184,6 +1186,29 @@ static int cluster_record(Engine* e) {
   return GS_OK;
 }
 
+// The stake reach view's two launches for the same recorded round (gs_reach.hip), each timed as
+// one launch of the family "reach".
+static int reach_record(Engine* e) {
+  if (!e->rc_on) return GS_OK;
+  hipEvent_t t0;
+  e->tbegin("reach", &t0);
+  hipError_t r = launch_reach_reduce(*e);
+  e->tend("reach", t0);
+  HIPC(r);
+  e->tbegin("reach", &t0);
+  r = launch_reach_fold(*e);
+  e->tend("reach", t0);
+  HIPC(r);
+  ++e->rc_rounds;
+  return GS_OK;
+}
+
+// the views behind a recorded round's last kernel
+static int views_record(Engine* e) {
+  if (int s = cluster_record(e)) return s;
+  return reach_record(e);
+}
+
 // The delivery tree of the recorded one-kernel round about to be launched (gs_tree_wg.hip): on the
 // engine's stream ahead of the round kernel, so it walks the rows and masks the round's BFS will.
 static int tree_record(Engine* e) {
@@ -1356,7 +1381,7 @@ static int do_stats(Engine* e, int mode) {
   hipError_t r = launch_stats(*e, e->sum_used, mode);
   e->tend("stats", t0);
   HIPC(r);
-  if (int s = cluster_record(e)) return s;
+  if (int s = views_record(e)) return s;
   if (++e->sum_used == e->sum_cap) return drain_summaries(e);
   return GS_OK;
 }
@@ -1433,7 +1458,7 @@ static int round_ahead(Engine* e, uint32_t round, bool rec) {
   e->rot_cnt_dirty = true;  // (the other counter was not zeroed)
   e->inb_valid = false;
   if (rec)
-    if (int s = cluster_record(e)) return s;
+    if (int s = views_record(e)) return s;
   if (rec && ++e->sum_used == e->sum_cap) return drain_summaries(e);
   return GS_OK;
 }
@@ -1517,7 +1542,8 @@ static int round_split(Engine* e, uint32_t round, bool rec) {
 
 int gs_round(gs_engine* eh, uint32_t round, int record) {
   ENGINE_NOJOIN(eh);
-  if (e->split_ok && e->fused && !e->cl_on && !e->tr_on && !e->part_on && round < (1u << 27) && e->slots_set)
+  if (e->split_ok && e->fused && !e->cl_on && !e->rc_on && !e->tr_on && !e->part_on && round < (1u << 27) &&
+      e->slots_set)
     return round_split(e, round, record != 0);
   if (int s = split_join(e)) return s;
   if (int s = refuse_part(e)) return s;
@@ -1549,7 +1575,7 @@ int gs_round(gs_engine* eh, uint32_t round, int record) {
     e->tend("rotate", t0);
     HIPC(r);
     if (rec)
-      if (int s = cluster_record(e)) return s;
+      if (int s = views_record(e)) return s;
     if (rec && ++e->sum_used == e->sum_cap) return drain_summaries(e);
     return GS_OK;
   }
@@ -2088,6 +2114,128 @@ int gs_read_cluster_rounds(gs_engine* eh, gs_cluster_round* out, size_t cap, siz
   return gs_read_cluster_rounds_group(eh, 0, out, cap, count);
 }
 
+// ------------------------------------------------- stake reach view ----
+static int reach_zero(Engine* e) {
+  e->rc_rounds = 0;
+  if (!e->rc_on) return GS_OK;
+  HIPC(hipMemsetAsync(e->rc_scr, 0, (size_t)e->rc_G * 256 * 3 * 8, e->st));
+  HIPC(hipMemsetAsync(e->rc_acc, 0, (size_t)e->rc_G * 6 * 256 * 8, e->st));
+  return GS_OK;
+}
+
+static void reach_free(Engine* e) {
+  dfree(*e, e->rc_scr, (size_t)e->rc_G * 256 * 3);
+  dfree(*e, e->rc_acc, (size_t)e->rc_G * 6 * 256);
+  dfree(*e, e->rc_chunks, std::max<size_t>(2, e->rc_nchunks));  // (at least 16 B each, as cluster_free's)
+  dfree(*e, e->rc_wts, std::max<size_t>(4, e->S));
+  e->rc_on = false;
+  e->rc_G = 0;
+  e->rc_nchunks = 0;
+  e->rc_rounds = 0;
+  e->rc_gsz.clear();
+  e->rc_w.clear();
+}
+
+// gs_reach_enable[_groups] behind the argument checks: `what` names the entry point in messages
+static int reach_enable(Engine* e, const std::vector<uint32_t>& gsz, const std::vector<uint32_t>& w,
+                        const std::string& what) {
+  if (e->rc_on) {  // the identical grouping again is a no-op; another one needs a disable first
+    if (e->rc_gsz == gsz && e->rc_w == w) return GS_OK;
+    return fail(GS_ESTATE, what + ": a view with another grouping or other weights is enabled; disable it first "
+                               "(gs_reach_enable(e, 0))");
+  }
+  // a round's limb sums of a group stay in u64: at most (sum of weights) x n_nodes terms below 2^32
+  for (size_t g = 0, a = 0; g < gsz.size(); a += gsz[g], ++g) {
+    uint64_t ws = 0;
+    for (uint32_t j = 0; j < gsz[g]; ++j) ws += w[a + j];
+    if (ws > 0xFFFFFFFFull / e->N)  // (ws x n_nodes >= 2^32, without the product)
+      return fail(GS_ERANGE, what + ": group " + std::to_string(g) + ": (sum of weights " + std::to_string(ws) +
+                                 ") x n_nodes must stay below 2^32");
+  }
+  const uint32_t G = (uint32_t)gsz.size();
+  const std::vector<ClusterChunk> plan = cluster_plan_build(e->NP, gsz.data(), G);
+  if (G > 65535 || plan.size() > 65535)
+    return fail(GS_ERANGE, what + ": more than 65,535 groups or slot chunks (a launch's grid limit)");
+  e->rc_G = G;  // (reach_free counts with it)
+  e->rc_nchunks = (uint32_t)plan.size();
+  int s = dalloc(*e, &e->rc_scr, (size_t)G * 256 * 3, 0);
+  if (!s) s = dalloc(*e, &e->rc_acc, (size_t)G * 6 * 256, 0);
+  if (!s) s = dalloc(*e, &e->rc_chunks, std::max<size_t>(2, plan.size()), 0);
+  if (!s) s = dalloc(*e, &e->rc_wts, std::max<size_t>(4, e->S), 0);
+  if (!s) {
+    hipError_t r = hipMemcpyAsync(e->rc_chunks, plan.data(), plan.size() * sizeof(ClusterChunk), hipMemcpyHostToDevice, e->st);
+    if (r == hipSuccess) r = hipMemcpyAsync(e->rc_wts, w.data(), (size_t)e->S * 4, hipMemcpyHostToDevice, e->st);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->st);  // (plan is a local)
+    if (r != hipSuccess) s = fail(GS_EHIP, what + ": " + hipGetErrorString(r));
+  }
+  if (s) {  // all or none
+    const std::string msg = g_err;
+    hipStreamSynchronize(e->st);
+    reach_free(e);
+    return fail(s, msg);
+  }
+  e->rc_on = true;
+  e->rc_gsz = gsz;
+  e->rc_w = w;
+  return GS_OK;
+}
+
+int gs_reach_enable(gs_engine* eh, int on) {
+  ENGINE(eh);
+  if (e->part_on)
+    return fail(GS_ESTATE, "gs_reach_enable: a node-range partition rank holds its own nodes' hops only (the "
+                           "partitioned view needs an exchange of the per-round sums)");
+  if (!on) {
+    if (!e->rc_on) return GS_OK;
+    HIPC(hipStreamSynchronize(e->st));
+    reach_free(e);
+    return GS_OK;
+  }
+  return reach_enable(e, std::vector<uint32_t>(1, e->S), std::vector<uint32_t>(e->S, 1u), "gs_reach_enable");
+}
+
+int gs_reach_enable_groups(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
+  ENGINE(eh);
+  if (e->part_on)
+    return fail(GS_ESTATE, "gs_reach_enable_groups: a node-range partition rank holds its own nodes' hops only (the "
+                           "partitioned view needs an exchange of the per-round sums)");
+  std::vector<uint32_t> gsz;
+  if (!group_slots) {
+    if (n_groups) return fail(GS_EINVAL, "gs_reach_enable_groups: group_slots is null but n_groups is not 0");
+    for (const TrajTab& t : e->traj) gsz.push_back(t.ns);  // one group per trajectory table (gs_create: one)
+  } else {
+    if (n_groups == 0 || n_groups > e->S)
+      return fail(GS_EINVAL, "gs_reach_enable_groups: n_groups must be within [1, n_slots]");
+    gsz.assign(group_slots, group_slots + n_groups);
+  }
+  uint64_t sum = 0;
+  for (size_t g = 0; g < gsz.size(); ++g) {
+    if (!gsz[g]) return fail(GS_EINVAL, "gs_reach_enable_groups: group_slots[" + std::to_string(g) + "] is an empty group");
+    sum += gsz[g];
+  }
+  if (sum != e->S)
+    return fail(GS_EINVAL, "gs_reach_enable_groups: group_slots sum to " + std::to_string(sum) + ", the engine has " +
+                               std::to_string(e->S) + " slots");
+  std::vector<uint32_t> w(e->S, 1u);
+  if (weights) w.assign(weights, weights + e->S);
+  return reach_enable(e, gsz, w, "gs_reach_enable_groups");
+}
+
+int gs_read_reach(gs_engine* eh, uint32_t g, uint64_t* nodes, uint64_t* stake_lo, uint64_t* stake_hi,
+                  uint64_t* last_nodes, uint64_t* last_stake_lo, uint64_t* last_stake_hi, uint64_t* rounds) {
+  ENGINE(eh);
+  if (!e->rc_on) return fail(GS_ESTATE, "the stake reach view is not enabled (gs_reach_enable)");
+  if (g >= e->rc_G) return fail(GS_EINVAL, "group out of range");
+  if (int s = check_err(e)) return s;
+  const uint64_t* a = e->rc_acc + (size_t)g * 6 * 256;
+  uint64_t* out[6] = {nodes, stake_lo, stake_hi, last_nodes, last_stake_lo, last_stake_hi};
+  for (int k = 0; k < 6; ++k)
+    if (out[k]) HIPC(hipMemcpyAsync(out[k], a + k * 256, 256 * 8, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  if (rounds) *rounds = e->rc_rounds;
+  return GS_OK;
+}
+
 int gs_read_failed(gs_engine* eh, uint32_t slot, uint8_t* failed) {
   ENGINE(eh);
   SLOT_CHECK(slot);
@@ -2173,7 +2321,7 @@ int gs_engine_round_kind(gs_engine* eh, uint32_t* fused) {
 int gs_engine_round_split(gs_engine* eh, uint32_t* out, size_t n) {
   ENGINE(eh);
   if (!out || n < 3) return fail(GS_EINVAL, "gs_engine_round_split: need 3 words");
-  const bool on = e->split_ok && e->fused && !e->cl_on && !e->tr_on && !e->part_on;  // (what gs_round checks)
+  const bool on = e->split_ok && e->fused && !e->cl_on && !e->rc_on && !e->tr_on && !e->part_on;  // (what gs_round checks)
   out[0] = on ? 1u : 0u;
   out[1] = on ? e->split_s0 : 0u;
   out[2] = on ? e->S - e->split_s0 : 0u;

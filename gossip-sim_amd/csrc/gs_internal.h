@@ -294,6 +294,18 @@ struct Engine {
   ClusterChunk* cl_chunks = nullptr;   // [cl_nchunks] gs_cluster_plan.h
   uint32_t cl_nchunks = 0;
   uint32_t* cl_wts = nullptr;          // [S]
+  // stake reach view (gs_reach_enable[_groups], gs_reach.hip): nodes and stake per hop byte, per
+  // group of consecutive slots with a weight per slot; independent of the cluster view
+  bool rc_on = false;
+  uint32_t rc_G = 0;
+  std::vector<uint32_t> rc_gsz;        // slots of each group
+  std::vector<uint32_t> rc_w;          // weight of each slot
+  uint64_t* rc_scr = nullptr;          // [G][256][3] this round's count / lo32 / hi32 sums (zero between recorded rounds)
+  uint64_t* rc_acc = nullptr;          // [G][6][256] nodes, stake lo, stake hi: totals, then the last recorded round's
+  ClusterChunk* rc_chunks = nullptr;   // [rc_nchunks] gs_cluster_plan.h
+  uint32_t rc_nchunks = 0;
+  uint32_t* rc_wts = nullptr;          // [S]
+  uint64_t rc_rounds = 0;              // recorded rounds since gs_set_slots (or the enable)
   // delivery tree (gs_tree_enable, gs_tree_wg.hip): first-discoverer parents and relay load per pair
   bool tr_on = false;
   uint32_t* tr_parent = nullptr;       // [PAIRS] the last recorded round's parents (UINT32_MAX: origin / unreached)
@@ -475,6 +487,9 @@ size_t tree_rec_btot_words(const Engine& e);
 // cluster load view (gs_cluster.hip): the recorded round's reduction over slots and its fold
 hipError_t launch_cluster_view(Engine& e, uint32_t rec_index);
 uint32_t cluster_chunk_slots(uint32_t NP, uint32_t S);
+// stake reach view (gs_reach.hip): the recorded round's two launches
+hipError_t launch_reach_reduce(Engine& e);
+hipError_t launch_reach_fold(Engine& e);
 hipError_t launch_gather_strided_u32(Engine& e, const uint32_t* src, size_t stride, uint32_t n, uint32_t* dst);
 
 }  // namespace gs

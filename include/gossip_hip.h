@@ -352,6 +352,46 @@ int gs_read_cluster_load_group(gs_engine* e, uint32_t g, uint64_t* egress, uint6
                                uint64_t* delivered, uint64_t* hop_sum, uint32_t* egress_peak,
                                uint32_t* ingress_peak);
 int gs_read_cluster_rounds_group(gs_engine* e, uint32_t g, gs_cluster_round* out, size_t cap, size_t* count);
+/* --- stake reach view: nodes and stake reached per hop, summed over the slots of a group ---
+ * The stake-weighted latency curve: how much stake holds a message after h hops. With h_j what
+ * gs_read_hops returns for slot j after a recorded round, w_j a u32 weight per slot and g a group
+ * of consecutive slots (gs_cluster_enable_groups' grouping and weight rules), for every hop byte
+ * b in 0..255:
+ *   nodes_g[b] = sum_{j in g} w_j #{v : h_j[v] == b}
+ *   stake_g[b] = sum_{j in g} w_j sum_{v : h_j[v] == b} stake[v]
+ * The bin is the byte as read: bin 0 holds the origins, bin 255 (GS_HOP_UNREACHED) everything
+ * unreached, failed nodes included. Per group the view keeps both arrays of the last recorded
+ * round, both summed over the recorded rounds since gs_set_slots (which zeroes them and the round
+ * count), and that count. All values are exact integers; stake values are 128 bits, returned as
+ * (lo, hi) u64 halves: value = hi << 64 | lo.
+ * gs_reach_enable(on != 0) is one group of unit weights; gs_reach_enable_groups takes
+ * gs_cluster_enable_groups' arguments (group_slots == NULL with n_groups == 0: one group per
+ * trajectory table; weights NULL = 1 each, 0 excludes the slot). Either is allowed whenever
+ * gs_set_slots is; allocation is all or nothing (GS_ENOMEM): 18 KB per group plus 12 B per slot
+ * chunk and 4 B per slot, counted in gs_engine_info's bytes and gs_engine_memory's other_bytes;
+ * gs_reach_enable(e, 0) frees either kind. GS_EINVAL (the message names the argument): counts
+ * that do not sum to n_slots, an empty group, n_groups > n_slots, a null group_slots with
+ * n_groups != 0. GS_ERANGE (the message names the group): a group whose (sum of weights) x
+ * n_nodes >= 2^32 -- the stakes are summed as 32-bit limbs and a round's limb sums stay u64;
+ * there is no limit on the stakes themselves -- or more than 65,535 groups or slot chunks.
+ * GS_ESTATE: a partition rank; a view with another grouping or other weights is enabled (disable
+ * it first); enabling the identical grouping again is a no-op, and one group of unit weights is
+ * gs_reach_enable's grouping. A refused call leaves the engine as it was. The view is independent
+ * of the cluster load view: both may be on at once, with different groupings.
+ * While enabled, every recorded round (gs_round with record != 0 on every path,
+ * gs_record_round) runs the reduction as exactly two launches behind the round's last kernel,
+ * whatever the group count (kernel family "reach": two launches counted per recorded round); a
+ * round that is not recorded launches nothing, an engine that never enables the view allocates
+ * and launches nothing, and the round split is off while the view is on (gs_engine_round_split
+ * reports it). Rounds recorded before the view was enabled are not in it.
+ * gs_read_reach reads group g (g >= n_groups: GS_EINVAL; no enabled view: GS_ESTATE); every
+ * array is [256], any pointer may be NULL. No reference interface. */
+int gs_reach_enable(gs_engine* e, int on);
+int gs_reach_enable_groups(gs_engine* e, const uint32_t* group_slots, uint32_t n_groups,
+                           const uint32_t* weights /*[n_slots] or NULL = 1*/);
+int gs_read_reach(gs_engine* e, uint32_t g, uint64_t* nodes /*[256]*/, uint64_t* stake_lo /*[256]*/,
+                  uint64_t* stake_hi /*[256]*/, uint64_t* last_nodes, uint64_t* last_stake_lo,
+                  uint64_t* last_stake_hi, uint64_t* rounds);
 /* Cluster::mst (gossip.rs:580-591): parent[v] = the node that first discovered v in the
  * reference's FIFO queue order, UINT32_MAX for the origin and unreached nodes (debug
  * readback after gs_run_gossip, n <= 262,144). */
@@ -408,7 +448,8 @@ int gs_read_tree_load(gs_engine* e, uint32_t slot, uint64_t* children /*[n]*/, u
                       uint64_t* rounds);
 /* GS_FLAG_PROFILE: summed device time of a kernel family ("bfs", "consume",
  * "rotate", "stats", "cluster": the cluster load view's two launches per recorded round,
- * "tree": the delivery tree's launch per recorded round)
+ * "tree": the delivery tree's launch per recorded round, "reach": the stake reach view's two
+ * launches per recorded round, each counted)
  * since the last reset, and its launch count. */
 int gs_kernel_time(gs_engine* e, const char* family, double* ms, uint64_t* launches);
 int gs_kernel_time_reset(gs_engine* e);
@@ -421,7 +462,7 @@ int gs_engine_memory(gs_engine* e, uint64_t* pair_bytes, uint64_t* other_bytes);
  * statistics per slot in one workgroup), 0 if it launches the step kernels. */
 int gs_engine_round_kind(gs_engine* e, uint32_t* fused);
 /* Round split (GS_ROUND_SPLIT, default on; =0 off): gs_round on a one-kernel engine with one
- * trajectory table, no cluster view, no partition and at least twice as many slots as round
+ * trajectory table, no cluster or reach view, no partition and at least twice as many slots as round
  * workgroups fit on the device launches the slots as two groups on two streams, so one group's
  * workgroups fill the compute units the other's launch leaves idle while it ends. Results are
  * the single-stream round's, bit for bit. out[0] 1 if gs_round splits now, out[1] / out[2] the
