@@ -166,6 +166,10 @@ EXPORTS = {
     "gs_reach_enable_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_read_reach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.POINTER(C.c_uint64)]),
+    "gs_tree_stake_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_tree_stake_enable_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_read_tree_stake": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_read_tree_stake_group": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.POINTER(C.c_uint64)]),
     "gs_destroy": (None, [C.c_void_p]),
     "gs_set_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "gs_set_slot_fanouts": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -728,6 +732,46 @@ class Engine:
         wide = lambda lo, hi: np.array([int(h) << 64 | int(l) for l, h in zip(lo, hi)], dtype=object)
         return {"nodes": a["nodes"], "stake": wide(a["lo"], a["hi"]), "last_nodes": a["last_nodes"],
                 "last_stake": wide(a["last_lo"], a["last_hi"]), "rounds": int(rounds.value)}
+
+    # --- delivery tree in stake (stake below each node, summed over a group's slots) ---
+    def enable_tree_stake(self, on=True, groups=None, weights=None):
+        """Allocates (or, on=False, frees) the delivery tree's view in stake: from now on every
+        recorded round with a tree mode on (enable_tree) also sums, per slot, the stake below each
+        node of the tree and, per slot group, the weighted children / subtree / below sums on the
+        device. groups / weights: as enable_cluster_view's."""
+        if not on:
+            if groups is not None or weights is not None:
+                raise ValueError("enable_tree_stake: groups / weights go with on=True")
+            _check(lib().gs_tree_stake_enable(self.h, 0))
+            return
+        if groups is None and weights is None:
+            _check(lib().gs_tree_stake_enable(self.h, 1))
+            return
+        g, w = cluster_group_args(self.n_slots, groups, weights)
+        _check(lib().gs_tree_stake_enable_groups(self.h, None if g is None else _ptr(g), 0 if g is None else len(g),
+                                                 None if w is None else _ptr(w)))
+
+    def tree_stake(self, slot):
+        """below[n] (u64) of the last recorded round: the stake of the nodes below each node in
+        the slot's delivery tree."""
+        below = np.zeros(self.n, dtype=np.uint64)
+        _check(lib().gs_read_tree_stake(self.h, slot, _ptr(below)))
+        return below
+
+    def tree_stake_load(self, group=None):
+        """Slot group `group` (None: group 0) of the view, per node: children / subtree / below
+        over the recorded rounds since set_slots, last_children / last_subtree / last_below of the
+        last recorded round, and rounds, their count. The counts are u64 [n]; below values pass
+        2^64, so they are object arrays of Python ints."""
+        keys = ("children", "subtree", "lo", "hi", "last_children", "last_subtree", "last_lo", "last_hi")
+        a = {k: np.zeros(self.n, dtype=np.uint64) for k in keys}
+        rounds = C.c_uint64()
+        _check(lib().gs_read_tree_stake_group(self.h, 0 if group is None else _group_index(group),
+                                              *[_ptr(a[k]) for k in keys], C.byref(rounds)))
+        wide = lambda lo, hi: np.array([int(h) << 64 | int(l) for l, h in zip(lo, hi)], dtype=object)
+        return {"children": a["children"], "subtree": a["subtree"], "below": wide(a["lo"], a["hi"]),
+                "last_children": a["last_children"], "last_subtree": a["last_subtree"],
+                "last_below": wide(a["last_lo"], a["last_hi"]), "rounds": int(rounds.value)}
 
     def failed(self, slot):
         out = np.zeros(self.n, dtype=np.uint8)

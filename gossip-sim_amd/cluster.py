@@ -63,6 +63,17 @@ def reach_curve(reach, fractions=(1 / 3, 1 / 2, 2 / 3)):
     return out
 
 
+def relay_stake_share(load, total_stake, rounds_weight):
+    """Per node, the exact share (fractions.Fraction) of the stake to deliver that heard its
+    messages through the node: Engine.tree_stake_load()'s "below" over total_stake x rounds_weight,
+    with total_stake the stake one message can reach (the network's, less the origin's where it
+    matters) and rounds_weight = recorded rounds x the group's sum of weights (1 with
+    "last_below" under the key "below" and unit weights of one slot). Zeros when that product is 0."""
+    from fractions import Fraction
+    den = int(total_stake) * int(rounds_weight)
+    return [Fraction(int(b), den) if den else Fraction(0) for b in load["below"]]
+
+
 def _spread(a):
     """min / median / p99 / max of a per-node array; the p99 is the value of rank
     ceil(0.99 n) in ascending order (an element of the array, no interpolation)."""

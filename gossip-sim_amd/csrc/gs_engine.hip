@@ -85,6 +85,8 @@ static int ensure_rot_ahead(Engine* e);
 static int cluster_zero(Engine* e);
 static int tree_zero(Engine* e);
 static int reach_zero(Engine* e);
+static int tstake_zero(Engine* e);
+static void tstake_free(Engine* e);
 
 template <class T>
 static void dfree(Engine& e, T*& p, size_t count) {
@@ -852,6 +854,7 @@ static int reset_pair_state(Engine* e) {
   e->h_cl.clear();
   if (int s = tree_zero(e)) return s;
   if (int s = reach_zero(e)) return s;
+  if (int s = tstake_zero(e)) return s;
   return cluster_zero(e);
 }
 
@@ -1234,6 +1237,7 @@ static int tree_zero(Engine* e) {
 }
 
 static void tree_free(Engine* e) {
+  tstake_free(e);  // (the view in stake reads this tree's parents)
   const size_t b0 = e->dev_bytes;
   dfree(*e, e->tr_parent, e->PAIRS);
   dfree(*e, e->tr_kids, e->PAIRS);
@@ -1375,6 +1379,182 @@ int gs_read_tree_load(gs_engine* eh, uint32_t slot, uint64_t* children, uint64_t
   return check_err(e);
 }
 
+// ------------------------------------------- delivery tree in stake ----
+// The view's three launches behind a recorded round whose tree pass ran (gs_tree_stake.hip): the
+// parents and the hop bytes are both final there. Each is timed as one launch of "tree_stake".
+static int tstake_record(Engine* e) {
+  if (!e->ts_on) return GS_OK;
+  hipError_t (*const step[3])(Engine&) = {launch_tstake_up, launch_tstake_reduce, launch_tstake_fold};
+  for (auto launch : step) {
+    hipEvent_t t0;
+    e->tbegin("tree_stake", &t0);
+    hipError_t r = launch(*e);
+    e->tend("tree_stake", t0);
+    HIPC(r);
+  }
+  ++e->ts_rounds;
+  return GS_OK;
+}
+
+static int tstake_zero(Engine* e) {
+  e->ts_rounds = 0;
+  if (!e->ts_on) return GS_OK;
+  HIPC(hipMemsetAsync(e->ts_below, 0, e->PAIRS * 8, e->st));
+  HIPC(hipMemsetAsync(e->ts_ks, 0, e->PAIRS * 4, e->st));
+  HIPC(hipMemsetAsync(e->ts_scr, 0, (size_t)e->ts_G * e->N * 4 * 8, e->st));
+  HIPC(hipMemsetAsync(e->ts_acc, 0, (size_t)e->ts_G * 8 * e->N * 8, e->st));
+  return GS_OK;
+}
+
+static void tstake_free(Engine* e) {
+  const size_t b0 = e->dev_bytes;
+  dfree(*e, e->ts_below, e->PAIRS);
+  dfree(*e, e->ts_ks, e->PAIRS);
+  e->pair_bytes -= b0 - e->dev_bytes;
+  dfree(*e, e->ts_scr, (size_t)e->ts_G * e->N * 4);
+  dfree(*e, e->ts_acc, (size_t)e->ts_G * 8 * e->N);
+  dfree(*e, e->ts_chunks, std::max<size_t>(2, e->ts_nchunks));  // (at least 16 B each, as cluster_free's)
+  dfree(*e, e->ts_wts, std::max<size_t>(4, e->S));
+  e->ts_on = false;
+  e->ts_G = 0;
+  e->ts_nchunks = 0;
+  e->ts_rounds = 0;
+  e->ts_gsz.clear();
+  e->ts_w.clear();
+}
+
+// gs_tree_stake_enable[_groups] behind the argument checks: `what` names the entry point in messages
+static int tstake_enable(Engine* e, const std::vector<uint32_t>& gsz, const std::vector<uint32_t>& w,
+                         const std::string& what) {
+  if (!e->tr_on)
+    return fail(GS_ESTATE, what + ": the view reads the delivery tree's parents; enable gs_tree_enable or "
+                               "gs_tree_enable_records first");
+  if (e->ts_on) {  // the identical grouping again is a no-op; another one needs a disable first
+    if (e->ts_gsz == gsz && e->ts_w == w) return GS_OK;
+    return fail(GS_ESTATE, what + ": a view with another grouping or other weights is enabled; disable it first "
+                               "(gs_tree_stake_enable(e, 0))");
+  }
+  const uint32_t nmax = tree_stake_max_nodes();
+  if (e->N > nmax)
+    return fail(GS_ERANGE, what + ": the per-slot kernel keeps " + std::to_string(tree_stake_node_bytes()) +
+                               " B of LDS per node: it serves at most " + std::to_string(nmax) + " nodes (160 KB)");
+  // the stake below the origin is at most the sum of all stakes, kept in u64
+  std::vector<uint64_t> st(e->N);
+  HIPC(hipMemcpyAsync(st.data(), e->stake, (size_t)e->N * 8, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  uint64_t total = 0;
+  for (uint64_t s : st) {
+    if (total + s < total) return fail(GS_ERANGE, what + ": the stakes must sum to less than 2^64 (the stake below a node is u64)");
+    total += s;
+  }
+  // a round's limb sums and weighted counts of a group stay in u64: at most (sum of weights) x n_nodes terms below 2^32
+  for (size_t g = 0, a = 0; g < gsz.size(); a += gsz[g], ++g) {
+    uint64_t ws = 0;
+    for (uint32_t j = 0; j < gsz[g]; ++j) ws += w[a + j];
+    if (ws > 0xFFFFFFFFull / e->N)  // (ws x n_nodes >= 2^32, without the product)
+      return fail(GS_ERANGE, what + ": group " + std::to_string(g) + ": (sum of weights " + std::to_string(ws) +
+                                 ") x n_nodes must stay below 2^32");
+  }
+  const uint32_t G = (uint32_t)gsz.size();
+  const std::vector<ClusterChunk> plan = cluster_plan_build(e->NP, gsz.data(), G);
+  if (G > 65535 || plan.size() > 65535)
+    return fail(GS_ERANGE, what + ": more than 65,535 groups or slot chunks (a launch's grid limit)");
+  e->ts_G = G;  // (tstake_free counts with it)
+  e->ts_nchunks = (uint32_t)plan.size();
+  const size_t b0 = e->dev_bytes;
+  int s = dalloc(*e, &e->ts_below, e->PAIRS, 0);
+  if (!s) s = dalloc(*e, &e->ts_ks, e->PAIRS, 0);
+  e->pair_bytes += e->dev_bytes - b0;
+  if (!s) s = dalloc(*e, &e->ts_scr, (size_t)G * e->N * 4, 0);
+  if (!s) s = dalloc(*e, &e->ts_acc, (size_t)G * 8 * e->N, 0);
+  if (!s) s = dalloc(*e, &e->ts_chunks, std::max<size_t>(2, plan.size()), 0);
+  if (!s) s = dalloc(*e, &e->ts_wts, std::max<size_t>(4, e->S), 0);
+  if (!s) {
+    hipError_t r = hipMemcpyAsync(e->ts_chunks, plan.data(), plan.size() * sizeof(ClusterChunk), hipMemcpyHostToDevice, e->st);
+    if (r == hipSuccess) r = hipMemcpyAsync(e->ts_wts, w.data(), (size_t)e->S * 4, hipMemcpyHostToDevice, e->st);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->st);  // (plan is a local)
+    if (r != hipSuccess) s = fail(GS_EHIP, what + ": " + hipGetErrorString(r));
+  }
+  if (s) {  // all or none
+    const std::string msg = g_err;
+    hipStreamSynchronize(e->st);
+    tstake_free(e);
+    return fail(s, msg);
+  }
+  e->ts_on = true;
+  e->ts_gsz = gsz;
+  e->ts_w = w;
+  return GS_OK;
+}
+
+int gs_tree_stake_enable(gs_engine* eh, int on) {
+  ENGINE(eh);
+  if (e->part_on)
+    return fail(GS_ESTATE, "gs_tree_stake_enable: a node-range partition rank runs no delivery tree");
+  if (!on) {
+    if (!e->ts_on) return GS_OK;
+    HIPC(hipStreamSynchronize(e->st));
+    tstake_free(e);
+    return GS_OK;
+  }
+  return tstake_enable(e, std::vector<uint32_t>(1, e->S), std::vector<uint32_t>(e->S, 1u), "gs_tree_stake_enable");
+}
+
+int gs_tree_stake_enable_groups(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
+  ENGINE(eh);
+  if (e->part_on)
+    return fail(GS_ESTATE, "gs_tree_stake_enable_groups: a node-range partition rank runs no delivery tree");
+  std::vector<uint32_t> gsz;
+  if (!group_slots) {
+    if (n_groups) return fail(GS_EINVAL, "gs_tree_stake_enable_groups: group_slots is null but n_groups is not 0");
+    for (const TrajTab& t : e->traj) gsz.push_back(t.ns);  // one group per trajectory table (gs_create: one)
+  } else {
+    if (n_groups == 0 || n_groups > e->S)
+      return fail(GS_EINVAL, "gs_tree_stake_enable_groups: n_groups must be within [1, n_slots]");
+    gsz.assign(group_slots, group_slots + n_groups);
+  }
+  uint64_t sum = 0;
+  for (size_t g = 0; g < gsz.size(); ++g) {
+    if (!gsz[g])
+      return fail(GS_EINVAL, "gs_tree_stake_enable_groups: group_slots[" + std::to_string(g) + "] is an empty group");
+    sum += gsz[g];
+  }
+  if (sum != e->S)
+    return fail(GS_EINVAL, "gs_tree_stake_enable_groups: group_slots sum to " + std::to_string(sum) +
+                               ", the engine has " + std::to_string(e->S) + " slots");
+  std::vector<uint32_t> w(e->S, 1u);
+  if (weights) w.assign(weights, weights + e->S);
+  return tstake_enable(e, gsz, w, "gs_tree_stake_enable_groups");
+}
+
+int gs_read_tree_stake(gs_engine* eh, uint32_t slot, uint64_t* below) {
+  ENGINE(eh);
+  if (slot >= e->S) return fail(GS_EINVAL, "slot out of range");
+  if (!below) return fail(GS_EINVAL, "null argument");
+  if (!e->ts_on) return fail(GS_ESTATE, "the delivery tree's stake view is not enabled (gs_tree_stake_enable)");
+  if (!e->ts_rounds) return fail(GS_ESTATE, "gs_read_tree_stake: no round has been recorded since the view was enabled or zeroed");
+  HIPC(hipMemcpyAsync(below, e->ts_below + (size_t)slot * e->N, (size_t)e->N * 8, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  return check_err(e);
+}
+
+int gs_read_tree_stake_group(gs_engine* eh, uint32_t g, uint64_t* children, uint64_t* subtree, uint64_t* below_lo,
+                             uint64_t* below_hi, uint64_t* last_children, uint64_t* last_subtree,
+                             uint64_t* last_below_lo, uint64_t* last_below_hi, uint64_t* rounds) {
+  ENGINE(eh);
+  if (!e->ts_on) return fail(GS_ESTATE, "the delivery tree's stake view is not enabled (gs_tree_stake_enable)");
+  if (g >= e->ts_G) return fail(GS_EINVAL, "group out of range");
+  if (!e->ts_rounds)
+    return fail(GS_ESTATE, "gs_read_tree_stake_group: no round has been recorded since the view was enabled or zeroed");
+  const uint64_t* a = e->ts_acc + (size_t)g * 8 * e->N;
+  uint64_t* out[8] = {children, subtree, below_lo, below_hi, last_children, last_subtree, last_below_lo, last_below_hi};
+  for (int k = 0; k < 8; ++k)
+    if (out[k]) HIPC(hipMemcpyAsync(out[k], a + (size_t)k * e->N, (size_t)e->N * 8, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  if (rounds) *rounds = e->ts_rounds;
+  return check_err(e);
+}
+
 static int do_stats(Engine* e, int mode) {
   hipEvent_t t0;
   e->tbegin("stats", &t0);
@@ -1457,8 +1637,10 @@ static int round_ahead(Engine* e, uint32_t round, bool rec) {
   e->rot_clear_pending = true;
   e->rot_cnt_dirty = true;  // (the other counter was not zeroed)
   e->inb_valid = false;
-  if (rec)
+  if (rec) {
     if (int s = views_record(e)) return s;
+    if (int s = tstake_record(e)) return s;
+  }
   if (rec && ++e->sum_used == e->sum_cap) return drain_summaries(e);
   return GS_OK;
 }
@@ -1574,8 +1756,10 @@ int gs_round(gs_engine* eh, uint32_t round, int record) {
     r = launch_rotate(*e, round, true);
     e->tend("rotate", t0);
     HIPC(r);
-    if (rec)
+    if (rec) {
       if (int s = views_record(e)) return s;
+      if (int s = tstake_record(e)) return s;
+    }
     if (rec && ++e->sum_used == e->sum_cap) return drain_summaries(e);
     return GS_OK;
   }
@@ -1598,7 +1782,10 @@ int gs_round(gs_engine* eh, uint32_t round, int record) {
   }
   if (int s = gs_chance_to_rotate(eh, round)) return s;
   if (rec && e->tr_rec) ++e->tr_rounds;
-  if (rec) return do_stats(e, e->bfs_mode == GS_BFS_WORKGROUP ? 2 : mv_layout(*e) ? 4 : 1);
+  if (rec) {
+    if (int s = do_stats(e, e->bfs_mode == GS_BFS_WORKGROUP ? 2 : mv_layout(*e) ? 4 : 1)) return s;
+    return e->tr_rec ? tstake_record(e) : GS_OK;  // (only where this round's tree pass ran)
+  }
   return GS_OK;
 }
 

@@ -322,6 +322,21 @@ struct Engine {
   uint32_t *trr_btot = nullptr, *trr_lv = nullptr, *trr_meta = nullptr;  // scan block totals, level starts, histogram
   uint32_t* trr_hmeta = nullptr;       // pinned [257]: the deepest level and each level's widest slot
   uint32_t trr_launches = 0;           // kernels of the last recorded round's pass
+  // delivery tree in stake (gs_tree_stake_enable[_groups], gs_tree_stake.hip): the stake below
+  // every node per pair, and per slot group the weighted children / subtree / below sums
+  bool ts_on = false;
+  uint32_t ts_G = 0;
+  std::vector<uint32_t> ts_gsz;        // slots of each group
+  std::vector<uint32_t> ts_w;          // weight of each slot
+  uint64_t* ts_below = nullptr;        // [PAIRS] the last recorded round's stake below each node
+  uint32_t* ts_ks = nullptr;           // [PAIRS] ... and its children << 16 | nodes below
+  uint64_t* ts_scr = nullptr;          // [G][N][4] this round's w kids / w sub / w lo32 / w hi32 sums (zero between rounds)
+  uint64_t* ts_acc = nullptr;          // [G][8][N] children, subtree, below lo, below hi: totals, then the last round's
+  ClusterChunk* ts_chunks = nullptr;   // [ts_nchunks] gs_cluster_plan.h
+  uint32_t ts_nchunks = 0;
+  uint32_t* ts_wts = nullptr;          // [S]
+  uint64_t ts_rounds = 0;              // recorded rounds since gs_set_slots (or the enable)
+  size_t ts_attr_lds = 0;              // dynamic LDS k_tstake_up was last configured for
   uint32_t* err = nullptr;
   uint32_t* h_err = nullptr;  // pinned
   unsigned long long* phase_clk = nullptr;  // GS_PHASE_PROFILE=1: per-phase workgroup clock sums
@@ -490,6 +505,14 @@ uint32_t cluster_chunk_slots(uint32_t NP, uint32_t S);
 // stake reach view (gs_reach.hip): the recorded round's two launches
 hipError_t launch_reach_reduce(Engine& e);
 hipError_t launch_reach_fold(Engine& e);
+// delivery tree in stake (gs_tree_stake.hip): the recorded round's three launches, and the
+// per-slot kernel's LDS bound
+hipError_t launch_tstake_up(Engine& e);
+hipError_t launch_tstake_reduce(Engine& e);
+hipError_t launch_tstake_fold(Engine& e);
+size_t tree_stake_lds_bytes(uint32_t N);
+uint32_t tree_stake_node_bytes();
+uint32_t tree_stake_max_nodes();
 hipError_t launch_gather_strided_u32(Engine& e, const uint32_t* src, size_t stride, uint32_t n, uint32_t* dst);
 
 }  // namespace gs

@@ -408,7 +408,7 @@ int gs_read_mst(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
  * the last two summed over the recorded rounds since gs_set_slots (which zeroes them and the
  * round count). gs_tree_enable(on != 0) allocates the three arrays (12 B per pair, counted in
  * gs_engine_info's bytes and gs_engine_memory's pair_bytes) and zeroes them; enabling an enabled
- * tree is a no-op; on == 0 frees them. Rounds that are not recorded launch nothing, an engine
+ * tree is a no-op; on == 0 frees them, and the view in stake (gs_tree_stake_enable) with them. Rounds that are not recorded launch nothing, an engine
  * that never enables the tree allocates and launches nothing, and the round split is off while
  * the tree is on (gs_engine_round_split reports it). GS_ESTATE: gs_round is not the one-kernel
  * round (gs_engine_round_kind == 0), or a partition rank. GS_ERANGE: more nodes than the
@@ -446,10 +446,58 @@ int gs_tree_enable_records(gs_engine* e, int on);
 int gs_read_tree(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
 int gs_read_tree_load(gs_engine* e, uint32_t slot, uint64_t* children /*[n]*/, uint64_t* subtree /*[n]*/,
                       uint64_t* rounds);
+/* --- delivery tree in stake: the stake below each node, per weighted slot group -----
+ * How much stake hears a message only through node v. With p_j what gs_read_tree returns for slot
+ * j after a recorded round, a node w is below v when v is a strict ancestor of w in p_j, and per
+ * slot and round
+ *   kids_j[v]  = #{w : p_j[w] = v}     sub_j[v] = #{w below v}
+ *   below_j[v] = sum_{w below v} stake[w]                                  (u64)
+ * (the origin's below is the stake of every reached non-origin node; unreached and failed nodes
+ * are below nobody and have nothing below them). With w_j a u32 weight per slot and g a group of
+ * consecutive slots (gs_cluster_enable_groups' grouping and weight rules), per group and round
+ *   K_g[v] = sum_{j in g} w_j kids_j[v]     S_g[v] = sum_{j in g} w_j sub_j[v]            (u64)
+ *   B_g[v] = sum_{j in g} w_j below_j[v]    (128 bits, returned as (lo, hi) u64 halves: hi << 64 | lo)
+ * Per group the view keeps K, S and B of the last recorded round, their sums over the recorded
+ * rounds since gs_set_slots (which zeroes them and the round count), and that count. All values
+ * are exact integers.
+ * gs_tree_stake_enable(on != 0) is one group of unit weights; gs_tree_stake_enable_groups takes
+ * gs_cluster_enable_groups' arguments (group_slots == NULL with n_groups == 0: one group per
+ * trajectory table; weights NULL = 1 each, 0 excludes the slot). A tree mode (gs_tree_enable or
+ * gs_tree_enable_records) must be on: GS_ESTATE otherwise, and turning the tree off frees this
+ * view as well. Allocation is all or nothing (GS_ENOMEM): 12 B per pair (the round's below and
+ * kids / sub), counted in gs_engine_info's bytes and gs_engine_memory's pair_bytes, and 96 B per
+ * (group, node), 12 B per slot chunk and 4 B per slot, counted as other bytes;
+ * gs_tree_stake_enable(e, 0) frees either kind. GS_EINVAL (the message names the argument): counts
+ * that do not sum to n_slots, an empty group, n_groups > n_slots, a null group_slots with
+ * n_groups != 0. GS_ERANGE (the message names the bound or the group): stakes that sum to 2^64 or
+ * more (below is u64); a group whose (sum of weights) x n_nodes >= 2^32 -- below is summed as
+ * 32-bit limbs and a round's limb sums and weighted counts stay u64; more than 65,535 groups or
+ * slot chunks; more nodes than the per-slot kernel's LDS holds (16 B per node of 160 KB: 10,175
+ * nodes). GS_ESTATE: a partition rank; a view with another grouping or other weights is enabled
+ * (disable it first); enabling the identical grouping again is a no-op, and one group of unit
+ * weights is gs_tree_stake_enable's grouping. A refused call leaves the engine as it was.
+ * While enabled, every recorded gs_round whose tree pass ran is followed by exactly three launches
+ * on the engine's stream behind the round's last kernel, whatever the group count (kernel family
+ * "tree_stake", each launch counted); a round that is not recorded launches nothing, and an engine
+ * that never enables the view allocates and launches nothing. Rounds recorded before the view was
+ * enabled are not in it. After a gs_round that raised the 253-hop error the view's arrays are
+ * unspecified, like the engine's other results.
+ * gs_read_tree_stake returns below_j of the last recorded round for one slot (slot >= n_slots:
+ * GS_EINVAL); gs_read_tree_stake_group reads group g (g >= n_groups: GS_EINVAL), every array [n],
+ * any pointer may be NULL. Both: GS_ESTATE without an enabled view or before a round is recorded.
+ * No reference interface. */
+int gs_tree_stake_enable(gs_engine* e, int on);
+int gs_tree_stake_enable_groups(gs_engine* e, const uint32_t* group_slots, uint32_t n_groups,
+                                const uint32_t* weights /*[n_slots] or NULL = 1*/);
+int gs_read_tree_stake(gs_engine* e, uint32_t slot, uint64_t* below /*[n]*/);
+int gs_read_tree_stake_group(gs_engine* e, uint32_t g, uint64_t* children, uint64_t* subtree, uint64_t* below_lo,
+                             uint64_t* below_hi, uint64_t* last_children, uint64_t* last_subtree,
+                             uint64_t* last_below_lo, uint64_t* last_below_hi, uint64_t* rounds);
 /* GS_FLAG_PROFILE: summed device time of a kernel family ("bfs", "consume",
  * "rotate", "stats", "cluster": the cluster load view's two launches per recorded round,
  * "tree": the delivery tree's launch per recorded round, "reach": the stake reach view's two
- * launches per recorded round, each counted)
+ * launches per recorded round, each counted, "tree_stake": the three launches of the delivery
+ * tree's view in stake per recorded round, each counted)
  * since the last reset, and its launch count. */
 int gs_kernel_time(gs_engine* e, const char* family, double* ms, uint64_t* launches);
 int gs_kernel_time_reset(gs_engine* e);

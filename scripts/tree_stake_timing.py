@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""What the delivery tree's view in stake costs per recorded round:
+kernel_time("tree_stake") beside kernel_time("tree") and kernel_time("round") of the same engine,
+on the C2 shape (3,000 nodes, all origins, the one-kernel round), with one group and with one
+group per slot, twice each. Every round is recorded; one JSON line per run. The last round's view
+is checked first on 16 sampled slots: the per-slot below against a Python walk of Engine.tree, and
+with per-slot groups the group's last_below against it."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import engine_bind as eb
+
+gs, synth = eb.gs, eb.synth
+
+
+def run(per_slot, warmup=20, steps=100):
+    n = s = 3000
+    _, st = synth.network(n)
+    eng = gs.Engine(st, s, seed=0x5EED0003, active_set_size=12, rotation_probability=0.013333,
+                    bfs_mode=gs.GS_BFS_WORKGROUP, profile=True)
+    eng.set_slots(list(range(n)))
+    eng.enable_tree()
+    eng.enable_tree_stake(groups=[1] * s if per_slot else None)
+    eng.init_active_sets()
+    for r in range(warmup):
+        eng.round(r, record=True)
+    eng.sync()
+    eng.kernel_time_reset()
+    for r in range(warmup, warmup + steps):
+        eng.round(r, record=True)
+    eng.sync()
+    fam = {f: eng.kernel_time(f) for f in ("tree_stake", "tree", "round")}
+    sti = [int(x) for x in st]
+    for j in range(0, s, s // 16):
+        parent, hops = eng.tree(j).tolist(), eng.hops(j).tolist()
+        below = [0] * n
+        for w in sorted((w for w in range(n) if parent[w] != 0xFFFFFFFF), key=lambda w: -hops[w]):
+            below[parent[w]] += below[w] + sti[w]
+        assert [int(x) for x in eng.tree_stake(j)] == below, j
+        if per_slot:
+            assert list(eng.tree_stake_load(j)["last_below"]) == below, j
+    assert eng.tree_stake_load()["rounds"] == warmup + steps
+    out = {"per_slot_groups": per_slot, "steps": steps,
+           "tree_stake_us_per_round": round(1e3 * fam["tree_stake"][0] / steps, 2),
+           "tree_stake_launches": fam["tree_stake"][1],
+           "tree_us_per_round": round(1e3 * fam["tree"][0] / steps, 2),
+           "round_us_per_round": round(1e3 * fam["round"][0] / steps, 2)}
+    print(json.dumps(out), flush=True)
+    eng.close()
+
+
+if __name__ == "__main__":
+    for rep in range(2):
+        run(False)
+        run(True)
