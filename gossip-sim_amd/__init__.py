@@ -168,6 +168,7 @@ EXPORTS = {
                                 C.c_void_p, C.POINTER(C.c_uint64)]),
     "gs_tree_stake_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_tree_stake_enable_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_tree_stake_enable_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_read_tree_stake": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_read_tree_stake_group": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.POINTER(C.c_uint64)]),
     "gs_destroy": (None, [C.c_void_p]),
@@ -734,22 +735,26 @@ class Engine:
                 "last_stake": wide(a["last_lo"], a["last_hi"]), "rounds": int(rounds.value)}
 
     # --- delivery tree in stake (stake below each node, summed over a group's slots) ---
-    def enable_tree_stake(self, on=True, groups=None, weights=None):
+    def enable_tree_stake(self, on=True, groups=None, weights=None, records=False):
         """Allocates (or, on=False, frees) the delivery tree's view in stake: from now on every
         recorded round with a tree mode on (enable_tree) also sums, per slot, the stake below each
         node of the tree and, per slot group, the weighted children / subtree / below sums on the
-        device. groups / weights: as enable_cluster_view's."""
+        device. groups / weights: as enable_cluster_view's. records=True: the mode that walks the
+        levels of enable_tree(records=True)'s tree in device memory, at any node count (the
+        default keeps a slot's tree on-chip: up to 10,175 nodes)."""
         if not on:
-            if groups is not None or weights is not None:
-                raise ValueError("enable_tree_stake: groups / weights go with on=True")
+            if groups is not None or weights is not None or records:
+                raise ValueError("enable_tree_stake: groups / weights / records go with on=True")
             _check(lib().gs_tree_stake_enable(self.h, 0))
             return
-        if groups is None and weights is None:
+        if groups is None and weights is None and not records:
             _check(lib().gs_tree_stake_enable(self.h, 1))
             return
+        if groups is None and weights is None:
+            groups = [self.n_slots]  # (one group of unit weights, as gs_tree_stake_enable's)
         g, w = cluster_group_args(self.n_slots, groups, weights)
-        _check(lib().gs_tree_stake_enable_groups(self.h, None if g is None else _ptr(g), 0 if g is None else len(g),
-                                                 None if w is None else _ptr(w)))
+        fn = lib().gs_tree_stake_enable_records if records else lib().gs_tree_stake_enable_groups
+        _check(fn(self.h, None if g is None else _ptr(g), 0 if g is None else len(g), None if w is None else _ptr(w)))
 
     def tree_stake(self, slot):
         """below[n] (u64) of the last recorded round: the stake of the nodes below each node in

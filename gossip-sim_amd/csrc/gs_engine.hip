@@ -1382,10 +1382,14 @@ int gs_read_tree_load(gs_engine* eh, uint32_t slot, uint64_t* children, uint64_t
 // ------------------------------------------- delivery tree in stake ----
 // The view's three launches behind a recorded round whose tree pass ran (gs_tree_stake.hip): the
 // parents and the hop bytes are both final there. Each is timed as one launch of "tree_stake".
+// The records mode (ts_rec) walks the records tree's levels instead (gs_tree_stake_rec.hip): wide
+// levels + runs of thin levels + 3 launches.
 static int tstake_record(Engine* e) {
   if (!e->ts_on) return GS_OK;
+  if (e->ts_rec) HIPC(launch_tstake_rec(*e));  // the level walk and the pack in k_tstake_up's place
   hipError_t (*const step[3])(Engine&) = {launch_tstake_up, launch_tstake_reduce, launch_tstake_fold};
   for (auto launch : step) {
+    if (e->ts_rec && launch == launch_tstake_up) continue;
     hipEvent_t t0;
     e->tbegin("tree_stake", &t0);
     hipError_t r = launch(*e);
@@ -1415,7 +1419,7 @@ static void tstake_free(Engine* e) {
   dfree(*e, e->ts_acc, (size_t)e->ts_G * 8 * e->N);
   dfree(*e, e->ts_chunks, std::max<size_t>(2, e->ts_nchunks));  // (at least 16 B each, as cluster_free's)
   dfree(*e, e->ts_wts, std::max<size_t>(4, e->S));
-  e->ts_on = false;
+  e->ts_on = e->ts_rec = false;
   e->ts_G = 0;
   e->ts_nchunks = 0;
   e->ts_rounds = 0;
@@ -1425,17 +1429,22 @@ static void tstake_free(Engine* e) {
 
 // gs_tree_stake_enable[_groups] behind the argument checks: `what` names the entry point in messages
 static int tstake_enable(Engine* e, const std::vector<uint32_t>& gsz, const std::vector<uint32_t>& w,
-                         const std::string& what) {
+                         const std::string& what, bool rec = false) {
+  if (rec && !e->tr_rec)
+    return fail(GS_ESTATE, what + ": the level walk reads what the records tree pass leaves in memory; enable "
+                               "gs_tree_enable_records first");
   if (!e->tr_on)
     return fail(GS_ESTATE, what + ": the view reads the delivery tree's parents; enable gs_tree_enable or "
                                "gs_tree_enable_records first");
+  if (e->ts_on && e->ts_rec != rec)
+    return fail(GS_ESTATE, what + ": the view's other kind is enabled; disable it first (gs_tree_stake_enable(e, 0))");
   if (e->ts_on) {  // the identical grouping again is a no-op; another one needs a disable first
     if (e->ts_gsz == gsz && e->ts_w == w) return GS_OK;
     return fail(GS_ESTATE, what + ": a view with another grouping or other weights is enabled; disable it first "
                                "(gs_tree_stake_enable(e, 0))");
   }
   const uint32_t nmax = tree_stake_max_nodes();
-  if (e->N > nmax)
+  if (!rec && e->N > nmax)
     return fail(GS_ERANGE, what + ": the per-slot kernel keeps " + std::to_string(tree_stake_node_bytes()) +
                                " B of LDS per node: it serves at most " + std::to_string(nmax) + " nodes (160 KB)");
   // the stake below the origin is at most the sum of all stakes, kept in u64
@@ -1482,6 +1491,7 @@ static int tstake_enable(Engine* e, const std::vector<uint32_t>& gsz, const std:
     return fail(s, msg);
   }
   e->ts_on = true;
+  e->ts_rec = rec;
   e->ts_gsz = gsz;
   e->ts_w = w;
   return GS_OK;
@@ -1500,31 +1510,40 @@ int gs_tree_stake_enable(gs_engine* eh, int on) {
   return tstake_enable(e, std::vector<uint32_t>(1, e->S), std::vector<uint32_t>(e->S, 1u), "gs_tree_stake_enable");
 }
 
-int gs_tree_stake_enable_groups(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
-  ENGINE(eh);
-  if (e->part_on)
-    return fail(GS_ESTATE, "gs_tree_stake_enable_groups: a node-range partition rank runs no delivery tree");
+// gs_tree_stake_enable_groups and gs_tree_stake_enable_records: one set of argument rules
+static int tstake_enable_groups(Engine* e, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights,
+                                const std::string& what, bool rec) {
+  if (e->part_on) return fail(GS_ESTATE, what + ": a node-range partition rank runs no delivery tree");
   std::vector<uint32_t> gsz;
   if (!group_slots) {
-    if (n_groups) return fail(GS_EINVAL, "gs_tree_stake_enable_groups: group_slots is null but n_groups is not 0");
+    if (n_groups) return fail(GS_EINVAL, what + ": group_slots is null but n_groups is not 0");
     for (const TrajTab& t : e->traj) gsz.push_back(t.ns);  // one group per trajectory table (gs_create: one)
   } else {
-    if (n_groups == 0 || n_groups > e->S)
-      return fail(GS_EINVAL, "gs_tree_stake_enable_groups: n_groups must be within [1, n_slots]");
+    if (n_groups == 0 || n_groups > e->S) return fail(GS_EINVAL, what + ": n_groups must be within [1, n_slots]");
     gsz.assign(group_slots, group_slots + n_groups);
   }
   uint64_t sum = 0;
   for (size_t g = 0; g < gsz.size(); ++g) {
-    if (!gsz[g])
-      return fail(GS_EINVAL, "gs_tree_stake_enable_groups: group_slots[" + std::to_string(g) + "] is an empty group");
+    if (!gsz[g]) return fail(GS_EINVAL, what + ": group_slots[" + std::to_string(g) + "] is an empty group");
     sum += gsz[g];
   }
   if (sum != e->S)
-    return fail(GS_EINVAL, "gs_tree_stake_enable_groups: group_slots sum to " + std::to_string(sum) +
-                               ", the engine has " + std::to_string(e->S) + " slots");
+    return fail(GS_EINVAL, what + ": group_slots sum to " + std::to_string(sum) + ", the engine has " +
+                               std::to_string(e->S) + " slots");
   std::vector<uint32_t> w(e->S, 1u);
   if (weights) w.assign(weights, weights + e->S);
-  return tstake_enable(e, gsz, w, "gs_tree_stake_enable_groups");
+  return tstake_enable(e, gsz, w, what, rec);
+}
+
+int gs_tree_stake_enable_groups(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
+  ENGINE(eh);
+  return tstake_enable_groups(e, group_slots, n_groups, weights, "gs_tree_stake_enable_groups", false);
+}
+
+// The view's records mode (gs_tree_stake_rec.hip): a level walk over the records tree's queue, at any node count.
+int gs_tree_stake_enable_records(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
+  ENGINE(eh);
+  return tstake_enable_groups(e, group_slots, n_groups, weights, "gs_tree_stake_enable_records", true);
 }
 
 int gs_read_tree_stake(gs_engine* eh, uint32_t slot, uint64_t* below) {

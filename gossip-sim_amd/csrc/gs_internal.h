@@ -325,11 +325,12 @@ struct Engine {
   // delivery tree in stake (gs_tree_stake_enable[_groups], gs_tree_stake.hip): the stake below
   // every node per pair, and per slot group the weighted children / subtree / below sums
   bool ts_on = false;
+  bool ts_rec = false;                 // the records mode (gs_tree_stake_enable_records, gs_tree_stake_rec.hip)
   uint32_t ts_G = 0;
   std::vector<uint32_t> ts_gsz;        // slots of each group
   std::vector<uint32_t> ts_w;          // weight of each slot
   uint64_t* ts_below = nullptr;        // [PAIRS] the last recorded round's stake below each node
-  uint32_t* ts_ks = nullptr;           // [PAIRS] ... and its children << 16 | nodes below
+  uint32_t* ts_ks = nullptr;           // [PAIRS] ... and its children << 16 | nodes below (ts_rec: << 24)
   uint64_t* ts_scr = nullptr;          // [G][N][4] this round's w kids / w sub / w lo32 / w hi32 sums (zero between rounds)
   uint64_t* ts_acc = nullptr;          // [G][8][N] children, subtree, below lo, below hi: totals, then the last round's
   ClusterChunk* ts_chunks = nullptr;   // [ts_nchunks] gs_cluster_plan.h
@@ -513,6 +514,9 @@ hipError_t launch_tstake_fold(Engine& e);
 size_t tree_stake_lds_bytes(uint32_t N);
 uint32_t tree_stake_node_bytes();
 uint32_t tree_stake_max_nodes();
+// its records mode (gs_tree_stake_rec.hip): the level walk and the pack in launch_tstake_up's
+// place, each launch timed as one of "tree_stake"
+hipError_t launch_tstake_rec(Engine& e);
 hipError_t launch_gather_strided_u32(Engine& e, const uint32_t* src, size_t stride, uint32_t n, uint32_t* dst);
 
 }  // namespace gs

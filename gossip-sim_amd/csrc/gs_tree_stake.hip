@@ -141,7 +141,9 @@ __global__ __launch_bounds__(TS_THREADS) void k_tstake_up(const uint32_t* __rest
   }
 }
 
-// grid (node blocks, chunks): blockIdx.y indexes the chunk table {group, s_lo, s_hi}
+// grid (node blocks, chunks): blockIdx.y indexes the chunk table {group, s_lo, s_hi}. SH: ks is
+// kids << SH | sub (16: k_tstake_up's; 24: the records mode's, gs_tree_stake_rec.hip)
+template <uint32_t SH>
 __global__ __launch_bounds__(256) void k_tstake_reduce(const u64* __restrict__ below, const uint32_t* __restrict__ ks,
                                                        uint32_t N, const uint3* __restrict__ chunks,
                                                        const uint32_t* __restrict__ wts, u64* __restrict__ scr) {
@@ -181,8 +183,8 @@ __global__ __launch_bounds__(256) void k_tstake_reduce(const u64* __restrict__ b
       }
 #pragma unroll
       for (uint32_t k = 0; k < 4; ++k) {
-        sk[k] += (u64)w * (k4[k] >> 16);
-        ss[k] += (u64)w * (k4[k] & 0xFFFFu);
+        sk[k] += (u64)w * (k4[k] >> SH);
+        ss[k] += (u64)w * (k4[k] & ((1u << SH) - 1u));
         sl[k] += (u64)w * (uint32_t)b[k];
         sh[k] += (u64)w * (uint32_t)(b[k] >> 32);
       }
@@ -267,9 +269,11 @@ hipError_t launch_tstake_up(Engine& e) {
 
 hipError_t launch_tstake_reduce(Engine& e) {
   const dim3 grid((e.N + TS_NODES - 1) / TS_NODES, e.ts_nchunks);
-  k_tstake_reduce<<<grid, 256, 0, e.st>>>(reinterpret_cast<const u64*>(e.ts_below), e.ts_ks, e.N,
-                                          reinterpret_cast<const uint3*>(e.ts_chunks), e.ts_wts,
-                                          reinterpret_cast<u64*>(e.ts_scr));
+  const u64* below = reinterpret_cast<const u64*>(e.ts_below);
+  const uint3* chunks = reinterpret_cast<const uint3*>(e.ts_chunks);
+  u64* scr = reinterpret_cast<u64*>(e.ts_scr);
+  if (e.ts_rec) k_tstake_reduce<24><<<grid, 256, 0, e.st>>>(below, e.ts_ks, e.N, chunks, e.ts_wts, scr);
+  else k_tstake_reduce<16><<<grid, 256, 0, e.st>>>(below, e.ts_ks, e.N, chunks, e.ts_wts, scr);
   return hipGetLastError();
 }
 

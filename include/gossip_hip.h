@@ -489,6 +489,16 @@ int gs_read_tree_load(gs_engine* e, uint32_t slot, uint64_t* children /*[n]*/, u
 int gs_tree_stake_enable(gs_engine* e, int on);
 int gs_tree_stake_enable_groups(gs_engine* e, const uint32_t* group_slots, uint32_t n_groups,
                                 const uint32_t* weights /*[n_slots] or NULL = 1*/);
+/* The records mode of the same view, at any node count gs_tree_enable_records serves: the same
+ * arguments, rules, memory (12 B per pair; kids << 24 | sub share the u32) and reads, without the
+ * 10,175-node bound. gs_tree_enable_records must be on (GS_ESTATE, the message names it). The two
+ * kinds are one view: while one is on, enabling the other is GS_ESTATE; gs_tree_stake_enable(e, 0)
+ * frees either, turning the tree off frees it, gs_set_slots zeroes it. A recorded round walks the
+ * levels of the records tree's queue in device memory, deepest first, with no host wait.
+ * Launches per recorded round ("tree_stake", each counted): (levels whose widest slot is above
+ * 256 nodes) + (maximal runs of consecutive levels of at most 256 nodes) + 3. */
+int gs_tree_stake_enable_records(gs_engine* e, const uint32_t* group_slots, uint32_t n_groups,
+                                 const uint32_t* weights /*[n_slots] or NULL = 1*/);
 int gs_read_tree_stake(gs_engine* e, uint32_t slot, uint64_t* below /*[n]*/);
 int gs_read_tree_stake_group(gs_engine* e, uint32_t g, uint64_t* children, uint64_t* subtree, uint64_t* below_lo,
                              uint64_t* below_hi, uint64_t* last_children, uint64_t* last_subtree,
@@ -497,7 +507,7 @@ int gs_read_tree_stake_group(gs_engine* e, uint32_t g, uint64_t* children, uint6
  * "rotate", "stats", "cluster": the cluster load view's two launches per recorded round,
  * "tree": the delivery tree's launch per recorded round, "reach": the stake reach view's two
  * launches per recorded round, each counted, "tree_stake": the three launches of the delivery
- * tree's view in stake per recorded round, each counted)
+ * tree's view in stake per recorded round, or its records mode's level launches + 3, each counted)
  * since the last reset, and its launch count. */
 int gs_kernel_time(gs_engine* e, const char* family, double* ms, uint64_t* launches);
 int gs_kernel_time_reset(gs_engine* e);
