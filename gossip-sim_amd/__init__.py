@@ -169,6 +169,8 @@ EXPORTS = {
     "gs_tree_stake_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_tree_stake_enable_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_tree_stake_enable_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_tree_stake_enable_dominators": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "gs_read_dominators": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_read_tree_stake": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "gs_read_tree_stake_group": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.POINTER(C.c_uint64)]),
     "gs_destroy": (None, [C.c_void_p]),
@@ -735,17 +737,28 @@ class Engine:
                 "last_stake": wide(a["last_lo"], a["last_hi"]), "rounds": int(rounds.value)}
 
     # --- delivery tree in stake (stake below each node, summed over a group's slots) ---
-    def enable_tree_stake(self, on=True, groups=None, weights=None, records=False):
+    def enable_tree_stake(self, on=True, groups=None, weights=None, records=False, dominators=False):
         """Allocates (or, on=False, frees) the delivery tree's view in stake: from now on every
         recorded round with a tree mode on (enable_tree) also sums, per slot, the stake below each
         node of the tree and, per slot group, the weighted children / subtree / below sums on the
         device. groups / weights: as enable_cluster_view's. records=True: the mode that walks the
         levels of enable_tree(records=True)'s tree in device memory, at any node count (the
-        default keeps a slot's tree on-chip: up to 10,175 nodes)."""
+        default keeps a slot's tree on-chip: up to 10,175 nodes). records=True, dominators=True:
+        the same sums over the dominator tree of the round's push graph: what the round cannot
+        deliver without the node, where the other kinds sum what first arrives through it."""
         if not on:
-            if groups is not None or weights is not None or records:
-                raise ValueError("enable_tree_stake: groups / weights / records go with on=True")
+            if groups is not None or weights is not None or records or dominators:
+                raise ValueError("enable_tree_stake: groups / weights / records / dominators go with on=True")
             _check(lib().gs_tree_stake_enable(self.h, 0))
+            return
+        if dominators:
+            if not records:
+                raise ValueError("enable_tree_stake: dominators=True reads the inbound records; pass records=True")
+            if groups is None and weights is None:
+                groups = [self.n_slots]
+            g, w = cluster_group_args(self.n_slots, groups, weights)
+            _check(lib().gs_tree_stake_enable_dominators(self.h, None if g is None else _ptr(g), 0 if g is None else len(g),
+                                                         None if w is None else _ptr(w)))
             return
         if groups is None and weights is None and not records:
             _check(lib().gs_tree_stake_enable(self.h, 1))
@@ -762,6 +775,14 @@ class Engine:
         below = np.zeros(self.n, dtype=np.uint64)
         _check(lib().gs_read_tree_stake(self.h, slot, _ptr(below)))
         return below
+
+    def dominators(self, slot):
+        """idom[n] (u32) of the last recorded round with enable_tree_stake(dominators=True) on: each
+        node's immediate dominator in the slot's push graph; 0xFFFFFFFF for the origin, unreached
+        and failed nodes."""
+        idom = np.zeros(self.n, dtype=np.uint32)
+        _check(lib().gs_read_dominators(self.h, slot, _ptr(idom)))
+        return idom
 
     def tree_stake_load(self, group=None):
         """Slot group `group` (None: group 0) of the view, per node: children / subtree / below

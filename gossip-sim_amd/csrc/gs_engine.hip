@@ -134,6 +134,7 @@ static void destroy_engine(Engine* e) {
   if (e->mv_hlvl) hipHostFree(e->mv_hlvl);
   if (e->mv_prof) hipHostFree(e->mv_prof);
   if (e->trr_hmeta) hipHostFree(e->trr_hmeta);
+  if (e->ts_hflag) hipHostFree(e->ts_hflag);
   if (e->pb_registered) pb_register(*e, false);
   for (auto& kv : e->timers)
     for (auto& pr : kv.second.ev) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
@@ -1383,13 +1384,21 @@ int gs_read_tree_load(gs_engine* eh, uint32_t slot, uint64_t* children, uint64_t
 // The view's three launches behind a recorded round whose tree pass ran (gs_tree_stake.hip): the
 // parents and the hop bytes are both final there. Each is timed as one launch of "tree_stake".
 // The records mode (ts_rec) walks the records tree's levels instead (gs_tree_stake_rec.hip): wide
-// levels + runs of thin levels + 3 launches.
+// levels + runs of thin levels + 3 launches. The dominator kind (ts_dom) puts its fixpoint and its
+// two walks over the dominator tree there (gs_tree_dom.hip).
 static int tstake_record(Engine* e) {
   if (!e->ts_on) return GS_OK;
   if (e->ts_rec) HIPC(launch_tstake_rec(*e));  // the level walk and the pack in k_tstake_up's place
+  if (e->ts_dom) {
+    bool capped = false;
+    HIPC(launch_tstake_dom(*e, &capped));
+    if (capped)
+      return fail(GS_ERANGE, "delivery dominators: " + std::to_string(TDOM_MAX_SWEEPS) +
+                                 " sweeps did not reach the fixpoint; the round is not in the view");
+  }
   hipError_t (*const step[3])(Engine&) = {launch_tstake_up, launch_tstake_reduce, launch_tstake_fold};
   for (auto launch : step) {
-    if (e->ts_rec && launch == launch_tstake_up) continue;
+    if ((e->ts_rec || e->ts_dom) && launch == launch_tstake_up) continue;
     hipEvent_t t0;
     e->tbegin("tree_stake", &t0);
     hipError_t r = launch(*e);
@@ -1404,7 +1413,8 @@ static int tstake_zero(Engine* e) {
   e->ts_rounds = 0;
   if (!e->ts_on) return GS_OK;
   HIPC(hipMemsetAsync(e->ts_below, 0, e->PAIRS * 8, e->st));
-  HIPC(hipMemsetAsync(e->ts_ks, 0, e->PAIRS * 4, e->st));
+  HIPC(hipMemsetAsync(e->ts_ks, 0, e->PAIRS * (e->ts_dom ? 8 : 4), e->st));
+  if (e->ts_dom) HIPC(hipMemsetAsync(e->ts_idom, 0xFF, e->PAIRS * 4, e->st));
   HIPC(hipMemsetAsync(e->ts_scr, 0, (size_t)e->ts_G * e->N * 4 * 8, e->st));
   HIPC(hipMemsetAsync(e->ts_acc, 0, (size_t)e->ts_G * 8 * e->N * 8, e->st));
   return GS_OK;
@@ -1413,13 +1423,17 @@ static int tstake_zero(Engine* e) {
 static void tstake_free(Engine* e) {
   const size_t b0 = e->dev_bytes;
   dfree(*e, e->ts_below, e->PAIRS);
-  dfree(*e, e->ts_ks, e->PAIRS);
+  dfree(*e, e->ts_ks, e->PAIRS * (e->ts_dom ? 2 : 1));
+  dfree(*e, e->ts_idom, e->PAIRS);
   e->pair_bytes -= b0 - e->dev_bytes;
+  dfree(*e, e->ts_flag, TDOM_MAX_SWEEPS);
+  if (e->ts_hflag) hipHostFree(e->ts_hflag);
+  e->ts_hflag = nullptr;
   dfree(*e, e->ts_scr, (size_t)e->ts_G * e->N * 4);
   dfree(*e, e->ts_acc, (size_t)e->ts_G * 8 * e->N);
   dfree(*e, e->ts_chunks, std::max<size_t>(2, e->ts_nchunks));  // (at least 16 B each, as cluster_free's)
   dfree(*e, e->ts_wts, std::max<size_t>(4, e->S));
-  e->ts_on = e->ts_rec = false;
+  e->ts_on = e->ts_rec = e->ts_dom = false;
   e->ts_G = 0;
   e->ts_nchunks = 0;
   e->ts_rounds = 0;
@@ -1429,22 +1443,22 @@ static void tstake_free(Engine* e) {
 
 // gs_tree_stake_enable[_groups] behind the argument checks: `what` names the entry point in messages
 static int tstake_enable(Engine* e, const std::vector<uint32_t>& gsz, const std::vector<uint32_t>& w,
-                         const std::string& what, bool rec = false) {
-  if (rec && !e->tr_rec)
+                         const std::string& what, bool rec = false, bool dom = false) {
+  if ((rec || dom) && !e->tr_rec)
     return fail(GS_ESTATE, what + ": the level walk reads what the records tree pass leaves in memory; enable "
                                "gs_tree_enable_records first");
   if (!e->tr_on)
     return fail(GS_ESTATE, what + ": the view reads the delivery tree's parents; enable gs_tree_enable or "
                                "gs_tree_enable_records first");
-  if (e->ts_on && e->ts_rec != rec)
-    return fail(GS_ESTATE, what + ": the view's other kind is enabled; disable it first (gs_tree_stake_enable(e, 0))");
+  if (e->ts_on && (e->ts_rec != rec || e->ts_dom != dom))
+    return fail(GS_ESTATE, what + ": another kind of the view is enabled; disable it first (gs_tree_stake_enable(e, 0))");
   if (e->ts_on) {  // the identical grouping again is a no-op; another one needs a disable first
     if (e->ts_gsz == gsz && e->ts_w == w) return GS_OK;
     return fail(GS_ESTATE, what + ": a view with another grouping or other weights is enabled; disable it first "
                                "(gs_tree_stake_enable(e, 0))");
   }
   const uint32_t nmax = tree_stake_max_nodes();
-  if (!rec && e->N > nmax)
+  if (!rec && !dom && e->N > nmax)
     return fail(GS_ERANGE, what + ": the per-slot kernel keeps " + std::to_string(tree_stake_node_bytes()) +
                                " B of LDS per node: it serves at most " + std::to_string(nmax) + " nodes (160 KB)");
   // the stake below the origin is at most the sum of all stakes, kept in u64
@@ -1472,8 +1486,12 @@ static int tstake_enable(Engine* e, const std::vector<uint32_t>& gsz, const std:
   e->ts_nchunks = (uint32_t)plan.size();
   const size_t b0 = e->dev_bytes;
   int s = dalloc(*e, &e->ts_below, e->PAIRS, 0);
-  if (!s) s = dalloc(*e, &e->ts_ks, e->PAIRS, 0);
+  e->ts_dom = dom;  // (tstake_free sizes ts_ks with it)
+  if (!s) s = dalloc(*e, &e->ts_ks, e->PAIRS * (dom ? 2 : 1), 0);
+  if (!s && dom) s = dalloc(*e, &e->ts_idom, e->PAIRS, 0xFF);
   e->pair_bytes += e->dev_bytes - b0;
+  if (!s && dom) s = dalloc(*e, &e->ts_flag, TDOM_MAX_SWEEPS, 0);
+  if (!s && dom && hipHostMalloc(&e->ts_hflag, 4) != hipSuccess) s = fail(GS_ENOMEM, what + ": pinned alloc");
   if (!s) s = dalloc(*e, &e->ts_scr, (size_t)G * e->N * 4, 0);
   if (!s) s = dalloc(*e, &e->ts_acc, (size_t)G * 8 * e->N, 0);
   if (!s) s = dalloc(*e, &e->ts_chunks, std::max<size_t>(2, plan.size()), 0);
@@ -1492,6 +1510,7 @@ static int tstake_enable(Engine* e, const std::vector<uint32_t>& gsz, const std:
   }
   e->ts_on = true;
   e->ts_rec = rec;
+  e->ts_dom = dom;
   e->ts_gsz = gsz;
   e->ts_w = w;
   return GS_OK;
@@ -1512,7 +1531,7 @@ int gs_tree_stake_enable(gs_engine* eh, int on) {
 
 // gs_tree_stake_enable_groups and gs_tree_stake_enable_records: one set of argument rules
 static int tstake_enable_groups(Engine* e, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights,
-                                const std::string& what, bool rec) {
+                                const std::string& what, bool rec, bool dom = false) {
   if (e->part_on) return fail(GS_ESTATE, what + ": a node-range partition rank runs no delivery tree");
   std::vector<uint32_t> gsz;
   if (!group_slots) {
@@ -1532,7 +1551,7 @@ static int tstake_enable_groups(Engine* e, const uint32_t* group_slots, uint32_t
                                std::to_string(e->S) + " slots");
   std::vector<uint32_t> w(e->S, 1u);
   if (weights) w.assign(weights, weights + e->S);
-  return tstake_enable(e, gsz, w, what, rec);
+  return tstake_enable(e, gsz, w, what, rec, dom);
 }
 
 int gs_tree_stake_enable_groups(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
@@ -1544,6 +1563,26 @@ int gs_tree_stake_enable_groups(gs_engine* eh, const uint32_t* group_slots, uint
 int gs_tree_stake_enable_records(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
   ENGINE(eh);
   return tstake_enable_groups(e, group_slots, n_groups, weights, "gs_tree_stake_enable_records", true);
+}
+
+// The view's dominator kind (gs_tree_dom.hip): the same sums over the dominator tree of the round's push graph.
+int gs_tree_stake_enable_dominators(gs_engine* eh, const uint32_t* group_slots, uint32_t n_groups, const uint32_t* weights) {
+  ENGINE(eh);
+  return tstake_enable_groups(e, group_slots, n_groups, weights, "gs_tree_stake_enable_dominators", false, true);
+}
+
+int gs_read_dominators(gs_engine* eh, uint32_t slot, uint32_t* idom) {
+  ENGINE(eh);
+  if (slot >= e->S) return fail(GS_EINVAL, "slot out of range");
+  if (!idom) return fail(GS_EINVAL, "null argument");
+  if (!e->ts_on || !e->ts_dom)
+    return fail(GS_ESTATE, "the view's dominator kind is not enabled (gs_tree_stake_enable_dominators)");
+  if (!e->ts_rounds) return fail(GS_ESTATE, "gs_read_dominators: no round has been recorded since the view was enabled or zeroed");
+  HIPC(hipMemcpyAsync(idom, e->ts_idom + (size_t)slot * e->N, (size_t)e->N * 4, hipMemcpyDeviceToHost, e->st));
+  HIPC(hipStreamSynchronize(e->st));
+  for (uint32_t v = 0; v < e->N; ++v)
+    if (idom[v] != UINT32_MAX) idom[v] &= 0xFFFFFFu;  // (the top byte is the dominator's hop)
+  return check_err(e);
 }
 
 int gs_read_tree_stake(gs_engine* eh, uint32_t slot, uint64_t* below) {
@@ -2472,6 +2511,11 @@ int gs_kernel_time(gs_engine* eh, const char* family, double* ms, uint64_t* laun
   if (family && std::strcmp(family, "tree.kernels") == 0) {  // kernels of the last records-mode tree pass
     *ms = 0;
     *launches = e->trr_launches;
+    return GS_OK;
+  }
+  if (family && std::strcmp(family, "tree_stake.sweeps") == 0) {  // sweeps of the last round's dominator fixpoint
+    *ms = 0;
+    *launches = e->ts_sweeps;
     return GS_OK;
   }
   if (family && std::strcmp(family, "round") == 0 && e->split_t_n) {

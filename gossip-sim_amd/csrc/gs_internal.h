@@ -338,6 +338,13 @@ struct Engine {
   uint32_t* ts_wts = nullptr;          // [S]
   uint64_t ts_rounds = 0;              // recorded rounds since gs_set_slots (or the enable)
   size_t ts_attr_lds = 0;              // dynamic LDS k_tstake_up was last configured for
+  // its dominator kind (gs_tree_stake_enable_dominators, gs_tree_dom.hip): the same arrays hold the
+  // dominator tree's sums; ts_ks is then [PAIRS] u64, children << 32 | nodes strictly dominated
+  bool ts_dom = false;
+  uint32_t* ts_idom = nullptr;         // [PAIRS] immediate dominator | its hop << 24 (UINT32_MAX: none)
+  uint32_t* ts_flag = nullptr;         // [TDOM_MAX_SWEEPS] word k: sweep k of the round changed a dominator
+  uint32_t* ts_hflag = nullptr;        // pinned [1]: the last sweep's word
+  uint32_t ts_sweeps = 0;              // sweeps of the last recorded round
   uint32_t* err = nullptr;
   uint32_t* h_err = nullptr;  // pinned
   unsigned long long* phase_clk = nullptr;  // GS_PHASE_PROFILE=1: per-phase workgroup clock sums
@@ -517,6 +524,13 @@ uint32_t tree_stake_max_nodes();
 // its records mode (gs_tree_stake_rec.hip): the level walk and the pack in launch_tstake_up's
 // place, each launch timed as one of "tree_stake"
 hipError_t launch_tstake_rec(Engine& e);
+// that mode's walk alone: below[] over the tree whose parents are pt (parent | any byte << 24)
+hipError_t launch_tstake_walk(Engine& e, const uint32_t* pt);
+// its dominator kind (gs_tree_dom.hip): the fixpoint's sweeps, the walk over the dominator tree and
+// the child / dominated counts in launch_tstake_rec's place, each launch timed as one of
+// "tree_stake". *capped: TDOM_MAX_SWEEPS sweeps did not reach the fixpoint (nothing was summed).
+constexpr uint32_t TDOM_MAX_SWEEPS = 1024;
+hipError_t launch_tstake_dom(Engine& e, bool* capped);
 hipError_t launch_gather_strided_u32(Engine& e, const uint32_t* src, size_t stride, uint32_t n, uint32_t* dst);
 
 }  // namespace gs

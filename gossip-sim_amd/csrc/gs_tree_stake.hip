@@ -141,10 +141,21 @@ __global__ __launch_bounds__(TS_THREADS) void k_tstake_up(const uint32_t* __rest
   }
 }
 
+// four consecutive kids / sub words, 16-byte aligned per load
+__device__ inline void load_ks4(const uint32_t* __restrict__ ks, uint32_t (&k4)[4]) {
+  const uint4 kk = *reinterpret_cast<const uint4*>(ks);
+  k4[0] = kk.x; k4[1] = kk.y; k4[2] = kk.z; k4[3] = kk.w;
+}
+__device__ inline void load_ks4(const u64* __restrict__ ks, u64 (&k4)[4]) {
+  const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(ks), k23 = *reinterpret_cast<const ulonglong2*>(ks + 2);
+  k4[0] = k01.x; k4[1] = k01.y; k4[2] = k23.x; k4[3] = k23.y;
+}
+
 // grid (node blocks, chunks): blockIdx.y indexes the chunk table {group, s_lo, s_hi}. SH: ks is
-// kids << SH | sub (16: k_tstake_up's; 24: the records mode's, gs_tree_stake_rec.hip)
-template <uint32_t SH>
-__global__ __launch_bounds__(256) void k_tstake_reduce(const u64* __restrict__ below, const uint32_t* __restrict__ ks,
+// kids << SH | sub (16: k_tstake_up's; 24: the records mode's, gs_tree_stake_rec.hip; 32 in a u64
+// word: the dominator kind's, gs_tree_dom.hip, where a node may have n - 1 children)
+template <uint32_t SH, typename KS = uint32_t>
+__global__ __launch_bounds__(256) void k_tstake_reduce(const u64* __restrict__ below, const KS* __restrict__ ks,
                                                        uint32_t N, const uint3* __restrict__ chunks,
                                                        const uint32_t* __restrict__ wts, u64* __restrict__ scr) {
   __shared__ u64 meet[TS_WORDS][4][64];  // [word][node of the lane][lane]: a lane's adds hit its own bank
@@ -166,13 +177,12 @@ __global__ __launch_bounds__(256) void k_tstake_reduce(const u64* __restrict__ b
       if (!w) continue;  // (uniform: the slot is not read at all)
       const size_t p = (size_t)j * N + v0;
       u64 b[4] = {0, 0, 0, 0};
-      uint32_t k4[4] = {0, 0, 0, 0};
-      if (nv == 4 && (p & 3) == 0) {  // 16-byte aligned: three wide loads
+      KS k4[4] = {0, 0, 0, 0};
+      if (nv == 4 && (p & 3) == 0) {  // 16-byte aligned: three wide loads (four with u64 counts)
         const ulonglong2 b01 = *reinterpret_cast<const ulonglong2*>(below + p);
         const ulonglong2 b23 = *reinterpret_cast<const ulonglong2*>(below + p + 2);
-        const uint4 kk = *reinterpret_cast<const uint4*>(ks + p);
         b[0] = b01.x; b[1] = b01.y; b[2] = b23.x; b[3] = b23.y;
-        k4[0] = kk.x; k4[1] = kk.y; k4[2] = kk.z; k4[3] = kk.w;
+        load_ks4(ks + p, k4);
       } else {
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k)
@@ -183,8 +193,8 @@ __global__ __launch_bounds__(256) void k_tstake_reduce(const u64* __restrict__ b
       }
 #pragma unroll
       for (uint32_t k = 0; k < 4; ++k) {
-        sk[k] += (u64)w * (k4[k] >> SH);
-        ss[k] += (u64)w * (k4[k] & ((1u << SH) - 1u));
+        sk[k] += (u64)w * (uint32_t)(k4[k] >> SH);
+        ss[k] += (u64)w * (uint32_t)(k4[k] & (((KS)1 << SH) - 1u));
         sl[k] += (u64)w * (uint32_t)b[k];
         sh[k] += (u64)w * (uint32_t)(b[k] >> 32);
       }
@@ -272,7 +282,9 @@ hipError_t launch_tstake_reduce(Engine& e) {
   const u64* below = reinterpret_cast<const u64*>(e.ts_below);
   const uint3* chunks = reinterpret_cast<const uint3*>(e.ts_chunks);
   u64* scr = reinterpret_cast<u64*>(e.ts_scr);
-  if (e.ts_rec) k_tstake_reduce<24><<<grid, 256, 0, e.st>>>(below, e.ts_ks, e.N, chunks, e.ts_wts, scr);
+  if (e.ts_dom)
+    k_tstake_reduce<32, u64><<<grid, 256, 0, e.st>>>(below, reinterpret_cast<const u64*>(e.ts_ks), e.N, chunks, e.ts_wts, scr);
+  else if (e.ts_rec) k_tstake_reduce<24><<<grid, 256, 0, e.st>>>(below, e.ts_ks, e.N, chunks, e.ts_wts, scr);
   else k_tstake_reduce<16><<<grid, 256, 0, e.st>>>(below, e.ts_ks, e.N, chunks, e.ts_wts, scr);
   return hipGetLastError();
 }

@@ -133,11 +133,11 @@ __global__ __launch_bounds__(TSR_B) void k_tsr_pack(const uint32_t* __restrict__
 
 }  // namespace
 
-// The records mode's walk and pack behind a recorded round whose records tree pass ran
-// (Engine::ts_rec), each launch timed as one of "tree_stake"; launch_tstake_reduce and
-// launch_tstake_fold follow. e.trr_hmeta is still this round's.
-hipError_t launch_tstake_rec(Engine& e) {
-  if (!e.trr_q || !e.trr_hmeta || !e.ts_below || e.PAIRS != (size_t)e.S * e.N) return hipErrorInvalidValue;
+// The walk behind a recorded round whose records tree pass ran, over the tree whose parents are pt
+// (the pass's own, or the dominator kind's: gs_tree_dom.hip), each launch timed as one of
+// "tree_stake". e.trr_hmeta is still this round's.
+hipError_t launch_tstake_walk(Engine& e, const uint32_t* pt) {
+  if (!e.trr_q || !e.trr_hmeta || !e.ts_below || !pt || e.PAIRS != (size_t)e.S * e.N) return hipErrorInvalidValue;
   u64* below = reinterpret_cast<u64*>(e.ts_below);
   hipError_t r = hipMemsetAsync(below, 0, e.PAIRS * 8, e.st);
   if (r != hipSuccess) return r;
@@ -149,19 +149,28 @@ hipError_t launch_tstake_rec(Engine& e) {
     if (!wmax[dd]) { --dd; continue; }  // (no slot has the level)
     e.tbegin("tree_stake", &t0);
     if (wmax[dd] > TSR_B) {
-      k_tsr_wide<<<dim3((wmax[dd] + TSR_B - 1) / TSR_B, e.S), TSR_B, 0, e.st>>>(e.trr_q, e.trr_pt, e.trr_lv, e.stake, below,
-                                                                              e.N, lvs, dd);
+      k_tsr_wide<<<dim3((wmax[dd] + TSR_B - 1) / TSR_B, e.S), TSR_B, 0, e.st>>>(e.trr_q, pt, e.trr_lv, e.stake, below, e.N,
+                                                                              lvs, dd);
       --dd;
     } else {
       uint32_t d_lo = dd;
       while (d_lo > 1 && wmax[d_lo - 1] <= TSR_B) --d_lo;  // (an empty level walks nothing)
-      k_tsr_thin<<<e.S, TSR_B, 0, e.st>>>(e.trr_q, e.trr_pt, e.trr_lv, e.stake, below, e.N, lvs, d_lo, dd);
+      k_tsr_thin<<<e.S, TSR_B, 0, e.st>>>(e.trr_q, pt, e.trr_lv, e.stake, below, e.N, lvs, d_lo, dd);
       dd = d_lo - 1;
     }
     r = hipGetLastError();
     e.tend("tree_stake", t0);
     if (r != hipSuccess) return r;
   }
+  return hipSuccess;
+}
+
+// The records mode's walk and pack (Engine::ts_rec); launch_tstake_reduce and launch_tstake_fold
+// follow.
+hipError_t launch_tstake_rec(Engine& e) {
+  hipError_t r = launch_tstake_walk(e, e.trr_pt);
+  if (r != hipSuccess) return r;
+  hipEvent_t t0;
   e.tbegin("tree_stake", &t0);
   k_tsr_pack<<<(uint32_t)((e.PAIRS + TSR_B * TSR_IT - 1) / (TSR_B * TSR_IT)), TSR_B, 0, e.st>>>(e.trr_cmask, e.trr_ex,
                                                                                              e.ts_ks, e.PAIRS);

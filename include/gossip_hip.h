@@ -447,7 +447,7 @@ int gs_read_tree(gs_engine* e, uint32_t slot, uint32_t* parent /*[n]*/);
 int gs_read_tree_load(gs_engine* e, uint32_t slot, uint64_t* children /*[n]*/, uint64_t* subtree /*[n]*/,
                       uint64_t* rounds);
 /* --- delivery tree in stake: the stake below each node, per weighted slot group -----
- * How much stake hears a message only through node v. With p_j what gs_read_tree returns for slot
+ * How much stake first hears a message through node v. With p_j what gs_read_tree returns for slot
  * j after a recorded round, a node w is below v when v is a strict ancestor of w in p_j, and per
  * slot and round
  *   kids_j[v]  = #{w : p_j[w] = v}     sub_j[v] = #{w below v}
@@ -499,6 +499,32 @@ int gs_tree_stake_enable_groups(gs_engine* e, const uint32_t* group_slots, uint3
  * 256 nodes) + (maximal runs of consecutive levels of at most 256 nodes) + 3. */
 int gs_tree_stake_enable_records(gs_engine* e, const uint32_t* group_slots, uint32_t n_groups,
                                  const uint32_t* weights /*[n_slots] or NULL = 1*/);
+/* The dominator kind of the same view: delivery dominators. The two kinds above sum over the tree
+ * of FIRST deliveries; a node below v there usually hears the message from other peers as well.
+ * Node v dominates w when every chain of recorded pushes from the origin to w passes through v;
+ * this kind computes, per slot, the immediate dominator idom_j[w] of every reached non-origin node
+ * from the round's complete inbound records, and the view's reads return the dominator tree's
+ * quantities in the same arrays: below_j[v] the stake of the nodes v strictly dominates (what the
+ * round's push graph cannot deliver without v), kids_j[v] the nodes whose immediate dominator is
+ * v, sub_j[v] the nodes v strictly dominates. gs_read_tree, gs_read_tree_load and the
+ * first-delivery arrays are untouched. The same arguments, grouping, weight and refusal rules and
+ * lifecycle as gs_tree_stake_enable_records: gs_tree_enable_records must be on (GS_ESTATE, the
+ * message names it); while any kind is on, enabling another is GS_ESTATE;
+ * gs_tree_stake_enable(e, 0) frees it, turning the tree off frees it, gs_set_slots zeroes it.
+ * Memory: 20 B per pair (below 8, kids << 32 | sub 8 -- a node may have n - 1 children here, so
+ * the counts do not share a u32 --, idom 4), counted as pair bytes; 4 KB of sweep words more in
+ * the other bytes. A recorded round runs sweeps of a monotone fixpoint over the records tree's
+ * levels until one changes nothing; the host reads one word back per sweep, and more than 1,024
+ * sweeps is GS_ERANGE (the round is then not in the view). Launches per recorded round
+ * ("tree_stake", each counted), with L1 = (levels whose widest slot is above 256 nodes) + (maximal
+ * runs of thinner levels) and L2 the same without level 1: 1 + sweeps x L2 + 2 x L1 + 2;
+ * gs_kernel_time("tree_stake.sweeps") gives the last round's sweeps (in `launches`).
+ * gs_read_dominators returns idom_j of the last recorded round (UINT32_MAX: the origin, unreached
+ * and failed nodes). slot >= n_slots: GS_EINVAL; without this kind enabled, or before a round is
+ * recorded: GS_ESTATE. No reference interface. */
+int gs_tree_stake_enable_dominators(gs_engine* e, const uint32_t* group_slots, uint32_t n_groups,
+                                    const uint32_t* weights /*[n_slots] or NULL = 1*/);
+int gs_read_dominators(gs_engine* e, uint32_t slot, uint32_t* idom /*[n]*/);
 int gs_read_tree_stake(gs_engine* e, uint32_t slot, uint64_t* below /*[n]*/);
 int gs_read_tree_stake_group(gs_engine* e, uint32_t g, uint64_t* children, uint64_t* subtree, uint64_t* below_lo,
                              uint64_t* below_hi, uint64_t* last_children, uint64_t* last_subtree,

@@ -7,7 +7,8 @@ is checked first on 16 sampled slots: the per-slot below against a Python walk o
 with per-slot groups the group's last_below against it.
 --records: the view's records mode at 100,000 nodes and 16 slots on the
 multi-source BFS with the records tree: "tree_stake" and "tree" time and launches per recorded
-round, and the launches a walk of one launch per level would have had; two slots are checked."""
+round, and the launches a walk of one launch per level would have had; two slots are checked.
+--dominators: the dominator kind at the same shape, beside the records mode."""
 import json
 import os
 import sys
@@ -98,7 +99,51 @@ def run_records(n=100_000, s=16, warmup=10, steps=100):
     eng.close()
 
 
+def run_dominators(n=100_000, s=16, warmup=10, steps=50):
+    """The dominator kind at the records mode's shape, beside the first-delivery
+    walk of an identical engine: both kinds' "tree_stake" and "tree" per recorded round, and the
+    sweeps per round (read after every round: a host wait outside the timed launches). Checked on
+    slot 0: below of the origin is every reached stake, and no node is below more stake in the
+    dominator tree than in the first-delivery tree."""
+    _, st = synth.network(n)
+    out = {"dominators": True, "nodes": n, "slots": s, "steps": steps}
+    below = {}
+    for kind in ("records", "dominators"):
+        eng = gs.Engine(st, s, seed=0x5EED0003, active_set_size=12, rotation_probability=0.013333,
+                        bfs_mode=gs.GS_BFS_MULTI, profile=True)
+        eng.set_slots([j * (n // s) for j in range(s)])
+        eng.enable_tree(records=True)
+        eng.enable_tree_stake(groups=[1] * s, records=True, dominators=kind == "dominators")
+        eng.init_active_sets()
+        sweeps = []
+        for r in range(warmup + steps):
+            if r == warmup:
+                eng.sync()
+                eng.kernel_time_reset()
+            eng.round(r, record=True)
+            if kind == "dominators" and r >= warmup:
+                sweeps.append(eng.kernel_time("tree_stake.sweeps")[1])
+        eng.sync()
+        fam = {f: eng.kernel_time(f) for f in ("tree_stake", "tree")}
+        below[kind] = eng.tree_stake(0)
+        out[kind + "_tree_stake_us_per_round"] = round(1e3 * fam["tree_stake"][0] / steps, 2)
+        out[kind + "_tree_stake_launches_per_round"] = fam["tree_stake"][1] / steps
+        out[kind + "_tree_us_per_round"] = round(1e3 * fam["tree"][0] / steps, 2)
+        if sweeps:
+            out["sweeps_per_round_mean"], out["sweeps_per_round_max"] = sum(sweeps) / len(sweeps), max(sweeps)
+            idom, parent = eng.dominators(0), eng.tree(0)
+            out["slot0_idom_not_parent"] = int((idom != parent).sum())
+            out["slot0_idom_not_parent_nor_origin"] = int(((idom != parent) & (idom != 0)).sum())
+        eng.close()
+    assert below["records"][0] == below["dominators"][0] > 0  # (slot 0's origin is node 0)
+    assert (below["dominators"] <= below["records"]).all()
+    print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
+    if "--dominators" in sys.argv[1:]:
+        run_dominators()
+        sys.exit(0)
     if "--records" in sys.argv[1:]:
         run_records()
         sys.exit(0)
